@@ -1,7 +1,12 @@
 """Benchmark: tracked frames/s (match + GN, 512x512 pointmaps) and BA edges/s.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   (N > 1: launched by torch.distributed.run, one rank per GPU, RCCL)
+
+A plain run sets up, warms up, times the K steps and prints the headline line (value, ms_per_step). With
+--dump-outputs DIR it also writes what the last timed step returned as DIR/<name>.npy. Everything else the
+benchmark measures (per-kernel HIP-event spans and rooflines, measured peaks, the BA legs, retrieval, the
+keyframe-store and per-config legs, the CPU baselines) runs only with --full.
 
 A "step" is one FrameTracker.track() of one frame against its keyframe on synthetic MASt3R-shaped
 outputs resident in HBM: fused matching (prep, iterative projection, occlusion, fp16 refine) +
@@ -63,7 +68,15 @@ def parse():
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
     ap.add_argument("--launch-probe", action="store_true",
                     help="test the N-rank launcher only (gloo, no GPU): rank 0 prints world size and a rank sum")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (float32 / float64)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every secondary leg: kernel spans and rooflines, peaks, BA, retrieval, store, "
+                         "configs, CPU baselines (the --no-* options select among them)")
+    args = ap.parse_args()
+    if args.steps < 1 and not args.launch_probe:
+        ap.error("--steps must be at least 1: value, ms_per_step and --dump-outputs come from the timed steps")
+    return args
 
 
 def sync_all(world):
@@ -79,6 +92,39 @@ def max_over_ranks(x, world):
     t = torch.tensor([x], dtype=torch.float64, device="cuda")
     dist.all_reduce(t, op=dist.ReduceOp.MAX)
     return float(t.item())
+
+
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays):
+    """Write each array as path/<name>.npy, float32 or float64 (other dtypes widen to float64; exact for the int64
+    pixel indices and flags here). The files hold at most DUMP_BUDGET_BYTES together: an array over its equal share
+    of the budget is cut to a fixed, seeded sample of its rows (sorted, the same rows in every run)."""
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_BUDGET_BYTES // max(len(arrays), 1)
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a)
+        if a.dtype not in (np.float32, np.float64):
+            a = a.astype(np.float64)
+        if a.nbytes > share and a.ndim >= 1 and a.shape[0] > 1:
+            row = a.nbytes // a.shape[0]
+            keep = max(share // row, 1)
+            a = a[np.sort(np.random.default_rng(0).choice(a.shape[0], keep, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
+def step_outputs(tracker, frame, new_kf, info):
+    """What a caller of FrameTracker.track(frame) receives: the frame's pose, the keyframe decision, the match_info
+    arrays (tracker.py:206) and the warm-start matches the tracker keeps for its next frame."""
+    host = lambda t: t.detach().cpu().numpy()
+    out = {"T_WC": host(frame.T_WC.data), "new_kf": np.array([float(new_kf)], dtype=np.float32),
+           "frame_id": np.array([float(frame.frame_id)])}  # which frame: warmup + steps - 1
+    for name, t in zip(("kf_X_canon", "kf_C_avg", "frame_X_canon", "frame_C_avg", "Qkf", "Qff"), info):
+        out[name] = host(t)
+    if tracker.idx_f2k is not None:
+        out["idx_f2k"] = host(tracker.idx_f2k).reshape(-1)
+    return out
 
 
 def bench_tracking(args, rank, world, dev):
@@ -107,17 +153,18 @@ def bench_tracking(args, rank, world, dev):
         # initial pose: the keyframe's (main.py:314-319 hands create_frame the last pose object; track()
         # replaces frame.T_WC rather than writing it, so sharing needs no clone)
         fr = Frame(i, (H, W), T_WC=kf.T_WC)
-        return tracker.track(fr)
+        return fr, tracker.track(fr)
 
     for i in range(args.warmup):
         step(i)
     iters = []
     step_s = []
+    calls0 = model.step  # the model is asked once per track(): its counter tells how many steps the timed loop ran
     sync_all(world)
     t0 = time.perf_counter()
     tp = t0
     for i in range(args.steps):
-        new_kf, _, reloc = step(args.warmup + i)
+        fr, (new_kf, info, reloc) = step(args.warmup + i)
         # track() returns once the frame's result is published to the host, so host stamps bracket each
         # frame's device work (the last fusion blocks overlap the next frame's host work)
         tn = time.perf_counter()
@@ -127,11 +174,14 @@ def bench_tracking(args, rank, world, dev):
         assert not reloc, "synthetic tracking failed"
     sync_all(world)
     elapsed = time.perf_counter() - t0
-    # Kernel durations: the same K steps again with HIP-event spans around every launch (libm3s,
+    timed_calls = model.step - calls0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, step_outputs(tracker, fr, new_kf, info))
+    # Kernel durations (--full): the same K steps again with HIP-event spans around every launch (libm3s,
     # on the launch stream). The event records cost host time in this sync-bound loop (~15%), so
     # they stay out of the pass that produces `value`.
     kern = {}
-    if not args.no_kernel_timing:
+    if args.full and not args.no_kernel_timing:
         lib.m3s_timing_reset()
         lib.m3s_timing_enable(1)
         for i in range(args.steps):
@@ -144,7 +194,7 @@ def bench_tracking(args, rank, world, dev):
             kern[name] = (ms.value, cnt.value)
         lib.m3s_timing_reset()
     elapsed = max_over_ranks(elapsed, world)
-    return elapsed, kern, float(np.mean(iters)), H * W, step_s
+    return elapsed, kern, float(np.mean(iters)), H * W, step_s, timed_calls
 
 
 def bench_configs(args, dev, frames=60, warmup=10):
@@ -811,7 +861,7 @@ def main():
             dist.init_process_group(backend)
     import __graft_entry__  # noqa: F401  (sys.path)
 
-    elapsed, kern, gn_iters, N, step_s = bench_tracking(args, rank, world, dev)
+    elapsed, kern, gn_iters, N, step_s, timed_calls = bench_tracking(args, rank, world, dev)
     total_frames = args.steps * world
     value = total_frames / elapsed
     rl = roofline(kern, N, gn_iters)
@@ -829,17 +879,18 @@ def main():
         roof["avg_us"] = d["avg_us"]
         roof["timing"] = "HIP events on the launch stream, second pass of the same K steps"
     frame = frame_roofline(step_s, N, gn_iters, args.mode)
-    peaks = measured_peaks(dev) if (rank == 0 and not args.no_peaks) else None
+    full = args.full  # the secondary legs below take runs of their own: only on request
+    peaks = measured_peaks(dev) if (full and rank == 0 and not args.no_peaks) else None
     ba = None
-    if not args.no_ba:
+    if full and not args.no_ba:
         ba = bench_ba(args, rank, world, dev, "C5")
         ba["c4"] = bench_ba(args, rank, world, dev, "C4")
         ba["eth3d"] = bench_ba(args, rank, world, dev, "C5e")
-    retrieval = bench_retrieval(dev) if (rank == 0 and not args.no_retrieval) else None
-    store = bench_store(args, dev) if (rank == 0 and not args.no_store) else None
-    configs = bench_configs(args, dev) if (rank == 0 and not args.no_store) else None
+    retrieval = bench_retrieval(dev) if (full and rank == 0 and not args.no_retrieval) else None
+    store = bench_store(args, dev) if (full and rank == 0 and not args.no_store) else None
+    configs = bench_configs(args, dev) if (full and rank == 0 and not args.no_store) else None
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if full and rank == 0 and world == 1 and not args.no_cpu:
         cpu = cpu_baseline(args)
         if ba is not None:
             ba["cpu_baseline"] = ba_cpu_baseline(args)
@@ -847,7 +898,7 @@ def main():
         rec = {
             "metric": "tracked frames/s (match+GN, 512x512 pointmaps) @1 GPU; BA edges/s @1/2/4/8",
             "value": value, "unit": "tracked frames/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True,
+            "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "full": full,
             "scaling": "weak", "vs_baseline": None, "dtype": "f32 (refine f16, GN accum f64)",
             "data": "synthetic MASt3R-shaped pointmaps/descriptors/confidences (no checkpoint, no dataset)",
             "config": {"workload": f"TUM fr1_room tracking-only, config/calib.yaml "
@@ -859,7 +910,7 @@ def main():
                                                              if "TORCHELASTIC_RUN_ID" in os.environ else
                                                              ("external" if world > 1 else "none")),
                                   "backend": dist.get_backend() if world > 1 else None},
-                       "gn_iters_mean": gn_iters, "ring_pairs": args.ring},
+                       "gn_iters_mean": gn_iters, "ring_pairs": args.ring, "timed_track_calls": timed_calls},
             "kernels_us": {k: round(v["avg_us"], 2) for k, v in rl.items()},
             "kernels": kernel_table(rl, N, gn_iters),
             "roofline": roof, "frame": frame, "peaks_measured": peaks, "cpu_baseline": cpu, "ba": ba,

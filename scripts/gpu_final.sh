@@ -5,6 +5,7 @@ set -o pipefail
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 mkdir -p gpurun_out
 bash scripts/gpu_check.sh || exit $?
-timeout -k 10 600 python bench.py > gpurun_out/bench_default.json 2> gpurun_out/bench_default.err
-rc=$?; echo "BENCH_RC=$rc"; tail -c 400 gpurun_out/bench_default.json; [ $rc -eq 0 ] || exit $rc
+# every leg of the benchmark at its default 100 steps: gpu_bench.sh runs `bench.py --full`, keeps the line and
+# its stderr as bench.json / bench.err beside this script's other records, and prints both
+STEPS=100 bash scripts/gpu_bench.sh || exit $?
 TAG=${TAG:-r03} bash scripts/gpu_prof_round.sh

@@ -14,7 +14,7 @@ cleanup() {
   du -sh gpurun_out
 }
 trap cleanup EXIT
-ARGS="--steps 20 --warmup 5 --no-cpu --no-ba --no-peaks --no-retrieval --no-store" bash scripts/gpu_prof.sh || exit $?
+ARGS="--steps 20 --warmup 5 --full --no-cpu --no-ba --no-peaks --no-retrieval --no-store" bash scripts/gpu_prof.sh || exit $?
 PROF_OUT=gpurun_out/summ python3 scripts/profile_summary.py gpurun_out/prof $TAG || exit $?
 # the two BA legs of the bench, each with its own trace and PMC passes: C5 (chess, calib, 384x512) and C4
 # (EuRoC MH_02, rays, 320x512), K = 256

@@ -6,8 +6,9 @@ cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 mkdir -p gpurun_out/prof_ba
 export TMPDIR=/tmp
 bash scripts/gpu_check.sh || exit $?
-timeout -k 10 600 python bench.py > gpurun_out/bench_default.json 2> gpurun_out/bench_default.err
-rc=$?; echo "BENCH_RC=$rc"; tail -c 600 gpurun_out/bench_default.json; [ $rc -eq 0 ] || exit $rc
+# every leg of the benchmark at its default 100 steps: gpu_bench.sh runs `bench.py --full`, keeps the line and
+# its stderr as bench.json / bench.err beside this script's other records, and prints both
+STEPS=100 bash scripts/gpu_bench.sh || exit $?
 bash scripts/gpu_prof.sh || exit $?
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof_ba/trace -o run -- python3 scripts/ba_exp.py 256 384 512 3 > gpurun_out/prof_ba/trace.log 2>&1
 echo "BA_TRACE_RC=$?"

@@ -9,5 +9,6 @@ rc=$?; echo "TRACK_TESTS_RC=$rc"; grep -E "PASS|FAIL|Error|error" gpurun_out/tra
 echo "== GN stamps (tracking, calib 512x512)"
 M3S_LIB=lightweight-mast3r-slam_amd/lib/exp/libm3s_gnst.so timeout -k 10 200 python3 scripts/gn_exp.py 2>&1 | grep -v amdgpu.ids || exit 1
 echo "== bench (tracking only)"
-timeout -k 10 300 python bench.py --steps 200 --warmup 20 --no-cpu --no-ba --no-peaks --no-retrieval > gpurun_out/bench_track.json 2> gpurun_out/bench_track.err
-rc=$?; echo "BENCH_RC=$rc"; python3 -c "import json;d=json.loads(open('gpurun_out/bench_track.json').read().strip().splitlines()[-1]);print(d['value'],d['ms_per_step'],d['kernels_us'],d['frame'])"
+# gpu_bench.sh runs `bench.py --full` with these selectors (kernels_us and frame need --full), keeps the line and
+# its stderr as bench.json / bench.err beside the test log, prints both and returns bench.py's exit code
+STEPS=200 bash scripts/gpu_bench.sh --warmup 20 --no-cpu --no-ba --no-peaks --no-retrieval
