@@ -35,7 +35,8 @@ hipError_t m3s_launch_refine_f32(const float*, const float*, const int64_t*, int
 hipError_t m3s_launch_refine_lin(const void*, const float*, const int*, int64_t*, int, int, int, int, int, int,
                                  void*, int*, const float*, hipStream_t);
 hipError_t m3s_launch_track_setup(const TrackArgs*, const TrackParams*, hipStream_t);
-hipError_t m3s_launch_track_iters(const TrackArgs*, const TrackParams*, int, int, int, int, hipStream_t);
+hipError_t m3s_launch_track_iters(const TrackArgs*, const TrackParams*, int, int, int, int, const TrackPublish*,
+                                  hipStream_t);
 hipError_t m3s_launch_fuse(const TrackArgs*, int, const FuseArgs*, int, int, const TrackPublish*, hipStream_t);
 hipError_t m3s_launch_track_init(const TrackArgs*, const float*, const float*, int, hipStream_t);
 int m3s_track_max_parts(void);
@@ -479,24 +480,35 @@ extern "C" int m3s_track(const m3s_track_inputs* in, const m3s_track_config* cfg
   if (mirror == nullptr) return fail(M3S_EHIP, "track: pinned result mirror allocation failed");
   static thread_local unsigned gen = 0;
   TrackPublish pub{mirror, a.tick + M3S_TRACK_PUBLISH_TICKET, ++gen};
+  const TrackPublish no_pub{nullptr, pub.ticket, 0u};
+  // The folded GN launch counts the unique matches and publishes the result itself, from its last block to leave:
+  // no kernel boundary and no second counting pass between the last solve and the host seeing the result.
+  // M3S_TRACK_PUBLISH_GN=0 keeps the count and the publish in the fuse launch (A/B), as does the separate setup.
+  const char* pubgn_env = getenv("M3S_TRACK_PUBLISH_GN");
+  const bool pub_gn = fold && !(pubgn_env != nullptr && pubgn_env[0] == '0');
   {
     Span sp("gn_iters", s);
-    HIP_TRY(m3s_launch_track_iters(&a, &p, nparts, p.max_iters, 0, fold, s), "track iterate launch");
+    HIP_TRY(m3s_launch_track_iters(&a, &p, nparts, p.max_iters, 0, fold, pub_gn ? &pub : &no_pub, s),
+            "track iterate launch");
   }
   // keyframe.update_pointmap(T_CkCf.act(Xkf), Ckf) after a successful solve (tracker.py:91-101): enqueued
-  // before the readback, it runs only if the solve finished with a pose
-  // The same launch publishes the result to the host mirror; the call returns once it has (the fusion
+  // before the readback, it runs only if the solve finished with a pose. It also clears the GN hand-off words and
+  // the counters for the next frame (behind the kernel boundary: GN blocks poll them until they exit) and, when the
+  // GN launch has not, counts the byte map and publishes. The call returns once the result is published (the fusion
   // blocks may still be running: later work on this stream is ordered after them).
-  HIP_TRY(m3s_launch_fuse(&a, 0, &fa, p.direct ? 0 : 1, N, &pub, s), "track fuse launch");
+  HIP_TRY(m3s_launch_fuse(&a, 0, &fa, (p.direct || pub_gn) ? 0 : 1, N, pub_gn ? &no_pub : &pub, s),
+          "track fuse launch");
   if (int rc = wait_published(mirror, pub.gen, s)) return rc;
-  {
-    std::lock_guard<std::mutex> lock(g_track_clean_mu);
-    g_track_clean[workspace] = {workspace_bytes, N};  // the fuse launch cleared what this frame dirtied
-  }
   const TrackState& hs = mirror->s;
-  if (hs.status == M3S_TRACK_STALLED)
+  if (hs.status == M3S_TRACK_STALLED)  // the scratch stays unrecorded: the next call on it runs track_init
     return fail(M3S_EHIP, "track: the persistent GN launch's hand-off stalled (its blocks were not co-resident); "
                           "no pose for this frame");
+  {
+    std::lock_guard<std::mutex> lock(g_track_clean_mu);
+    // this frame's launches clear what it dirtied: the byte map by whoever counted it, the rest by the fuse launch,
+    // which the next frame's kernels are stream-ordered behind
+    g_track_clean[workspace] = {workspace_bytes, N};
+  }
   memcpy(result->T_WCf, hs.T_WCf, sizeof(result->T_WCf));
   memcpy(result->T_CkCf, hs.T, sizeof(result->T_CkCf));
   result->cost = hs.last_cost;

@@ -10,6 +10,10 @@
 #define M3S_TRACK_STALLED 5  // the persistent GN launch lost a hand-off (blocks not co-resident): an error, not a result
 
 #define M3S_TRACK_SHARDS 8  // counter shards (one per XCD: blocks are dealt to XCDs round-robin)
+// A shard's counter line holds 16 64-bit words: word 0 the packed valid counts, word M3S_TRACK_UNIQUE_WORD the
+// shard's publish ticket when the GN launch publishes: {unique-match count : 32, stalled blocks : 16, arrivals : 16}
+// summed over the shard's blocks. The top publish ticket (M3S_TRACK_PUBLISH_TICKET, 64-bit there) has the same layout.
+#define M3S_TRACK_UNIQUE_WORD 1
 
 // Device-resident GN state (one per tracked frame). Layout mirrored by m3s/_track.py (M3S_TRACK_STATE_*).
 struct TrackState {
@@ -63,22 +67,24 @@ struct TrackArgs {
 };
 
 // The tick region (zeroed per frame by track_init): one 128-B line per XCD shard ticket of the persistent GN
-// launch (monotonic within the frame), the fuse kernel's publish ticket (one line), then the shard-sum granules
+// launch (monotonic within the frame), the publish ticket (one line; taken by the GN launch's blocks, or by the fuse
+// kernel's counting blocks with M3S_TRACK_PUBLISH_GN=0, and re-armed by its last arriver), then the shard-sum granules
 // of the GN launch: [2 iteration parities][8 shards][72] 8-byte {32-bit half of a shard sum, iteration + 1}.
 #define M3S_TRACK_PUBLISH_TICKET (M3S_TRACK_SHARDS * 32)
 #define M3S_TRACK_GRANULES ((M3S_TRACK_SHARDS + 1) * 32)
 #define M3S_TRACK_TICK_WORDS (M3S_TRACK_GRANULES + 2 * M3S_TRACK_SHARDS * 72 * 2)
 
 // The frame's result as the host reads it: a copy of the final TrackState in fine-grained (coherent)
-// pinned host memory, written by the fuse launch once n_unique is complete and then released with the
-// call's generation number; the host spins on gen instead of a D2H copy + hipStreamSynchronize.
+// pinned host memory, written once n_unique is complete (by the last GN block to leave, or by the fuse launch with
+// M3S_TRACK_PUBLISH_GN=0) and then released with the call's generation number; the host spins on gen instead of a
+// D2H copy + hipStreamSynchronize.
 struct TrackMirror {
   TrackState s;
   unsigned gen;
   unsigned pad[3];
 };
 struct TrackPublish {
-  TrackMirror* mirror;  // host pointer (the same address on the device for hipHostMalloc memory)
+  TrackMirror* mirror;  // host pointer (the same address on the device for hipHostMalloc memory); null: this launch does not publish
   unsigned* ticket;     // tick + M3S_TRACK_PUBLISH_TICKET (zeroed by track_init)
   unsigned gen;
 };

@@ -18,8 +18,12 @@
 //                  write-through (sc1) and takes an arrival ticket; the last-arriving block reduces all
 //                  partials, solves the 7x7 system, retracts T <- Exp(tau) T, applies the convergence
 //                  test, broadcasts the new T (GnBcast) and, once done, writes T_WCf = T_WCk T_CkCf
-//                  (also to the caller's T_out); the other blocks poll the broadcast and go on.
-//   fuse         : keyframe X <- (C X + C' T_CkCf Xkf) / (C + C'), C += C'
+//                  (also to the caller's T_out); the other blocks poll the broadcast and go on. The folded launch
+//                  also counts unique(idx[valid]) from the byte map while the first solve runs, and its last
+//                  block to leave publishes the frame's result to the host mirror (M3S_TRACK_PUBLISH_GN).
+//   fuse         : keyframe X <- (C X + C' T_CkCf Xkf) / (C + C'), C += C'; clears the GN hand-off words and the
+//                  counters for the next frame; with M3S_TRACK_PUBLISH_GN=0 (or the separate setup) it also counts
+//                  the byte map and publishes
 #include "m3s_common.hpp"
 #include "m3s_track.h"
 
@@ -87,8 +91,17 @@ __device__ void track_state_init(TrackState* st, const float* T_WCf, const float
 // ------------------------------------------------------------------------------------------
 // the 32-byte GN record of point n < N (r0, r1), its validity for the solve (v_opt) and for the keyframe stats
 // (v_kf), and the unique-match byte map entry
+// The byte-map mark. wt: write-through (sc1), for a GN launch that counts the map itself: its readers sit on other
+// XCDs inside the same launch, where a plain store is still in this XCD's L2 (no kernel boundary writes it back).
+__device__ __forceinline__ void mark_flag(uint8_t* flags, int64_t i, bool wt) {
+  if (wt)
+    __hip_atomic_store(&flags[i], (uint8_t)1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  else
+    flags[i] = 1;
+}
+
 __device__ __forceinline__ void setup_point(const TrackArgs& a, const TrackParams& p, int n, float4& r0, float4& r1,
-                                            int& v_opt, int& v_kf) {
+                                            int& v_opt, int& v_kf, bool wt_flags = false) {
   if (p.direct) {  // opt_pose_* surface: Qff = Qk, valid_match = valid, Xf pre-gathered
     const float qk = a.Qff[n];
     const bool valid_opt = a.valid_match[n] != 0;
@@ -116,7 +129,7 @@ __device__ __forceinline__ void setup_point(const TrackArgs& a, const TrackParam
     const bool valid_opt = vm && (cf > p.C_conf) && (ck > p.C_conf) && (qk > p.Q_conf);
     v_opt = valid_opt;
     v_kf = vm && (qk > p.Q_conf);
-    if (vm) a.flags[i] = 1;  // benign same-value races; popcounted by the fuse launch
+    if (vm) mark_flag(a.flags, i, wt_flags);  // benign same-value races; popcounted after the iteration-0 hand-off
     const float sq = valid_opt ? sqrtf(qk) : 0.0f;
     const float* Xf = a.Xf + i * 3;
     const float* Xk = a.Xk + (size_t)n * 3;
@@ -149,7 +162,7 @@ __device__ __forceinline__ void setup_point(const TrackArgs& a, const TrackParam
 // so the records and counts are the same bit for bit.
 template <int K>
 __device__ __forceinline__ void setup_points(const TrackArgs& a, const TrackParams& p, const int (&nn)[K],
-                                             float4 (&r0)[K], float4 (&r1)[K], int& v_opt, int& v_kf) {
+                                             float4 (&r0)[K], float4 (&r1)[K], int& v_opt, int& v_kf, bool wt_flags) {
   int n[K];
   bool act[K];
   int64_t i[K];
@@ -208,7 +221,7 @@ __device__ __forceinline__ void setup_points(const TrackArgs& a, const TrackPara
   }
 #pragma unroll
   for (int u = 0; u < K; u++)
-    if (act[u] && vm[u]) a.flags[i[u]] = 1;  // benign same-value races; popcounted by the fuse launch
+    if (act[u] && vm[u]) mark_flag(a.flags, i[u], wt_flags);  // benign same-value races
 }
 
 __global__ void __launch_bounds__(256) track_setup_kernel(TrackArgs a, TrackParams p) {
@@ -662,15 +675,61 @@ __device__ __forceinline__ void gn_flush(double* acc, const gf2* a2) {
   for (int c = 0; c < GN_NSUM; c++) acc[c] += (double)a2[c].x + (double)a2[c].y;
 }
 
+// ---- the unique-match count inside the folded GN launch (M3S_TRACK_PUBLISH_GN, the default) ----
+// Once a block has seen the iteration-0 shard sums, every block's marks are in memory: they were stored write-through
+// and drained (the vmcnt(0) in front of each block's iteration-0 ticket), and every shard sum follows all of its
+// shard's tickets. Waves 1..3 of every block then count and clear the map with sc1 loads and stores while wave 0's
+// first lane runs the iteration-0 solve: entry i of the n16 16-byte entries belongs to counting thread i % (blocks x
+// 192), and the thread that counted an entry clears it. The block's count waits in LDS and rides the block's arrival
+// at the publish tickets (the kernel's tail): nothing of it is on the hand-off chain.
+#define GN_COUNT_THREADS (GN_THREADS - 64)
+static_assert(GN_THREADS > 64, "the map is counted by the waves that do not solve");
+
+__device__ __forceinline__ int map_popc_clear(gull* fl, int i, unsigned long long m0, unsigned long long m1) {
+  __hip_atomic_store(&fl[2 * (size_t)i], 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  __hip_atomic_store(&fl[2 * (size_t)i + 1], 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  return __popcll(m0) + __popcll(m1);
+}
+
+// entries first, first + stride, ... < n16
+__device__ __forceinline__ int map_count_clear(gull* fl, int first, int n16, int stride) {
+  int cnt = 0;
+  for (int i = first; i < n16; i += stride) {
+    const unsigned long long m0 = __hip_atomic_load(&fl[2 * (size_t)i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const unsigned long long m1 = __hip_atomic_load(&fl[2 * (size_t)i + 1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    cnt += map_popc_clear(fl, i, m0, m1);
+  }
+  return cnt;
+}
+
+__device__ __forceinline__ int wave_sum_int(int v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+  return v;
+}
+
 //
 // SETUP (folded setup, M3S_TRACK_FOLD_SETUP=1): no track_setup launch. Every block derives the initial T_CkCf
 // itself (track_state_init's arithmetic), builds its points' records in the first iteration (setup_point: the
 // first round into registers, later rounds also into the record buffer for the later iterations), and adds its
 // valid counts to the shard counters before its iteration-0 ticket; the skip test (tracker.py:67-70) then reads the
 // counters after the iteration-0 hand-off, before the first solve, and block 0 writes the whole final state.
+//
+// PUBLISH (SETUP launches with pub.mirror set): the launch also counts the unique-match map (above) and publishes
+// the frame's result. Every block leaves through one tail, whatever ended it (converged, max iterations, skipped,
+// Cholesky failure, stalled hand-off): its thread 0 arrives once, with a relaxed add that never waits, at its XCD
+// shard's ticket (256 arrivals at one word would queue for ~3 us, MI355X_MICROARCH.md "fanin"), and the arrival that
+// completes a shard arrives for it at the top ticket. The added word carries the block's unique-match count and a
+// stalled mark besides the arrival, so the arrival that completes the top ticket holds the frame's n_unique in the
+// value its add returned. Every block holds the same final state in registers, so that arriver builds the TrackState
+// itself, writes the host mirror and releases the generation at system scope, then re-arms the top ticket (the shard
+// tickets lie in the counter lines the fuse launch clears). A frame that ended before the count ran (skipped, or
+// stalled at iteration 0) counts and clears the map in the tail.
 template <bool SETUP>
-__global__ void __launch_bounds__(GN_THREADS) gn_loop_kernel(TrackArgs a, TrackParams p) {
+__global__ void __launch_bounds__(GN_THREADS) gn_loop_kernel(TrackArgs a, TrackParams p, TrackPublish pub) {
   TrackState* st = a.state;
+  const bool pubgn = SETUP && pub.mirror != nullptr;
+  const bool ucount = pubgn && !p.direct;  // direct mode has no byte map
   float T[8];
   double old;  // the convergence test's previous cost (inf before the first solve)
   unsigned long long counts = 0;
@@ -709,6 +768,12 @@ __global__ void __launch_bounds__(GN_THREADS) gn_loop_kernel(TrackArgs a, TrackP
   __shared__ int s_last, s_stop, s_fin;
   __shared__ float s_T[8];
   __shared__ unsigned long long s_cnt[GN_THREADS / 64];  // SETUP: per-wave valid counts
+  __shared__ int s_ucnt[GN_THREADS / 64];                // PUBLISH: per-wave unique-match counts (waves 1..)
+  gull* fl = (gull*)a.flags;                             // the byte map as 8-byte halves of its 16-byte entries
+  const int n16 = (p.N + 15) / 16;
+  const int ct = blockIdx.x * GN_COUNT_THREADS + (int)threadIdx.x - 64;  // counting thread (waves 1..)
+  const int cstride = gridDim.x * GN_COUNT_THREADS;
+  bool counted = false, stalled = false;
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
   const unsigned nblk = gridDim.x;
   const int shard = blockIdx.x % M3S_TRACK_SHARDS;
@@ -728,7 +793,7 @@ __global__ void __launch_bounds__(GN_THREADS) gn_loop_kernel(TrackArgs a, TrackP
     int nn[GN_PPT];
 #pragma unroll
     for (int u = 0; u < GN_PPT; u++) nn[u] = n00 + u * stride;
-    setup_points<GN_PPT>(a, p, nn, c0, c1, v_opt, v_kf);
+    setup_points<GN_PPT>(a, p, nn, c0, c1, v_opt, v_kf, ucount);
   } else {
 #pragma unroll
     for (int u = 0; u < GN_PPT; u++) {
@@ -737,7 +802,7 @@ __global__ void __launch_bounds__(GN_THREADS) gn_loop_kernel(TrackArgs a, TrackP
         c0[u] = c1[u] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
         if (n < p.N) {
           int vo = 0, vk = 0;
-          setup_point(a, p, n, c0[u], c1[u], vo, vk);
+          setup_point(a, p, n, c0[u], c1[u], vo, vk, ucount);
           v_opt += vo;
           v_kf += vk;
         }
@@ -787,7 +852,7 @@ __global__ void __launch_bounds__(GN_THREADS) gn_loop_kernel(TrackArgs a, TrackP
           r0[u] = r1[u] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
           if (n0 + u * stride < p.N) {
             int vo = 0, vk = 0;
-            setup_point(a, p, n, r0[u], r1[u], vo, vk);
+            setup_point(a, p, n, r0[u], r1[u], vo, vk, ucount);
             v_opt += vo;
             v_kf += vk;
             float4* w = reinterpret_cast<float4*>(a.rec) + 2 * (size_t)n;
@@ -917,9 +982,19 @@ __global__ void __launch_bounds__(GN_THREADS) gn_loop_kernel(TrackArgs a, TrackP
         wt(&st->status, M3S_TRACK_STALLED);
         wt(&st->done, 1);
       }
-      return;
+      if (!pubgn) return;
+      status = M3S_TRACK_STALLED;  // PUBLISH: through the tail, so the frame is published and the host raises
+      stalled = true;
+      break;
     }
     GN_STAMP(5);
+    // PUBLISH: waves 1.. issue the load of their first map entry here and use it while lane 0 solves
+    const bool cnow = SETUP && ucount && it == 0;
+    unsigned long long m0 = 0ull, m1 = 0ull;
+    if (cnow && wid > 0 && ct < n16) {
+      m0 = __hip_atomic_load(&fl[2 * (size_t)ct], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      m1 = __hip_atomic_load(&fl[2 * (size_t)ct + 1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
     if (threadIdx.x < GN_NSUM) {  // the frame's sums: the shard sums in shard order
       const int c = threadIdx.x;
       double v = s_shard[0][c];
@@ -956,8 +1031,17 @@ __global__ void __launch_bounds__(GN_THREADS) gn_loop_kernel(TrackArgs a, TrackP
       cost = r.cost;
       iters_done = r.iter;
       status = r.status;
+    } else if (cnow && wid > 0) {  // meanwhile: the map counted and cleared (the rest of wave 0 idles as before)
+      int c = 0;
+      // the loaded halves are first touched here: without this the popcount, and with it the wait for the loads,
+      // moved up to the loads, in front of the barrier the solving lane waits at
+      asm volatile("" : "+v"(m0), "+v"(m1));
+      if (ct < n16) c = map_popc_clear(fl, ct, m0, m1) + map_count_clear(fl, ct + cstride, n16, cstride);
+      c = wave_sum_int(c);
+      if (lane == 0) s_ucnt[wid] = c;
     }
     __syncthreads();
+    if (cnow) counted = true;  // s_ucnt keeps the block's count until its arrival in the tail
     GN_STAMP(6);
 #pragma unroll
     for (int c = 0; c < 8; c++) T[c] = s_T[c];
@@ -965,9 +1049,31 @@ __global__ void __launch_bounds__(GN_THREADS) gn_loop_kernel(TrackArgs a, TrackP
     __syncthreads();  // s_T / s_fin are rewritten in the next iteration
     if (fin) break;
   }
-  // the final state, written by ONE block (plain stores of a single writer; the host and the fuse launch read it
-  // after this launch); every block holds the same values
-  if (SETUP && blockIdx.x == 0 && threadIdx.x == 0) {  // the whole state: track_state_init + the GN launch's writes
+  if (pubgn) {  // PUBLISH tail: no block waits for another here
+    if (ucount && !counted && wid > 0) {  // ended before the count ran: this block's entries now
+      const int c = wave_sum_int(map_count_clear(fl, ct, n16, cstride));
+      if (lane == 0) s_ucnt[wid] = c;
+    }
+    __syncthreads();
+  }
+  // the final state, written by ONE block (plain stores of a single writer; the fuse launch reads it after this
+  // launch); every block holds the same values, and with PUBLISH the last block to arrive publishes them
+  if (SETUP && threadIdx.x == 0 && (blockIdx.x == 0 || pubgn)) {  // the whole state: track_state_init + the GN launch's writes
+    // the arrival word: {unique-match count : 32, stalled blocks : 16, arrivals : 16}. A block adds its own to its
+    // shard's ticket; the add that completes a shard carries the shard's totals on to the top ticket, and the add
+    // that completes the top ticket has the frame's: the counts travel in the returned values, so the publisher
+    // loads nothing
+    unsigned long long arrive = 0ull, ticket = 0ull;
+    if (pubgn) {
+      unsigned tot = 0u;
+      if (ucount) {
+#pragma unroll
+        for (int w = 1; w < GN_THREADS / 64; w++) tot += (unsigned)s_ucnt[w];
+      }
+      arrive = ((unsigned long long)tot << 32) | (stalled ? 0x10000ull : 0ull) | 1ull;
+      ticket = __hip_atomic_fetch_add(&a.cnt[16 * shard + M3S_TRACK_UNIQUE_WORD], arrive, __ATOMIC_RELAXED,
+                                      __HIP_MEMORY_SCOPE_AGENT);
+    }
     TrackState v{};
 #pragma unroll
     for (int c = 0; c < 8; c++) v.T_WCk[c] = a.T_WCk[c];
@@ -987,14 +1093,30 @@ __global__ void __launch_bounds__(GN_THREADS) gn_loop_kernel(TrackArgs a, TrackP
       for (int c = 0; c < 8; c++) v.T[c] = T[c];
       if (status == M3S_TRACK_OK || status == M3S_TRACK_MAX_ITERS) {
         sim3_mul_norm(v.T_WCk, T, v.T_WCf);  // T_WCf = T_WCk * T_CkCf
-        if (a.T_out != nullptr)
-          for (int c = 0; c < 8; c++) {
-            a.T_out[c] = v.T_WCf[c];
-            a.T_out[8 + c] = T[c];
-          }
       }
     }
-    *st = v;
+    ticket += arrive;
+    if (pubgn && (ticket & 0xffffull) == per) {  // this shard is complete: one arrival at the top ticket for it
+      const unsigned long long up = (ticket & ~0xffffull) | 1ull;
+      const unsigned long long top =
+          __hip_atomic_fetch_add((gull*)pub.ticket, up, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + up;
+      if ((top & 0xffffull) == (unsigned long long)nsh) {  // every block of every shard has arrived
+        TrackState h = v;
+        h.n_unique = (int)(unsigned)(top >> 32);
+        if (((top >> 16) & 0xffffull) != 0ull) h.status = M3S_TRACK_STALLED;  // some block lost a hand-off
+        pub.mirror->s = h;
+        __hip_atomic_store(&pub.mirror->gen, pub.gen, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+        __hip_atomic_store((gull*)pub.ticket, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // re-armed
+      }
+    }
+    if (blockIdx.x == 0) {
+      if ((status == M3S_TRACK_OK || status == M3S_TRACK_MAX_ITERS) && a.T_out != nullptr)
+        for (int c = 0; c < 8; c++) {
+          a.T_out[c] = v.T_WCf[c];
+          a.T_out[8 + c] = T[c];
+        }
+      *st = v;
+    }
   }
   if (!SETUP && blockIdx.x == 0 && threadIdx.x == 0) {
     st->iter = iters_done;
@@ -1038,7 +1160,10 @@ __device__ void publish_state(const TrackState* st, TrackPublish pub) {
 
 // The counting blocks also leave the frame's scratch clean for the next frame on this workspace (the host then
 // skips track_init): the unique-idx byte map (each entry zeroed by the thread that counted it), the setup
-// counters, the GN shard tickets and granules (the publish ticket is re-armed by its last arriver).
+// counters, the GN shard tickets and granules (the publish ticket is re-armed by its last arriver). When the GN
+// launch has counted, cleared the map and published (pub.mirror null, no n_unique, clean_map 0), these blocks only
+// clear the tickets, granules and counters: that stays behind the kernel boundary, because GN blocks poll them until
+// they exit.
 __global__ void __launch_bounds__(256) fuse_kernel(const TrackState* __restrict__ st, int chunk_id, FuseArgs f,
                                                    int N, uint8_t* __restrict__ flags, int* __restrict__ n_unique,
                                                    TrackPublish pub, int clean_map, unsigned* __restrict__ tick,
@@ -1142,15 +1267,18 @@ extern "C" int m3s_track_max_parts(void) {
 
 // one persistent launch runs every GN iteration (iters and chunk_id are kept for the call sites); fold: the setup
 // runs inside it (gn_loop_kernel<true>, no track_setup launch before it)
+// pub->mirror set (folded launches only): the launch also counts the unique matches and publishes the result, and the
+// fuse launch behind it gets no mirror and no count
 extern "C" hipError_t m3s_launch_track_iters(const TrackArgs* a, const TrackParams* p, int nparts, int iters,
-                                             int chunk_id, int fold, hipStream_t s) {
+                                             int chunk_id, int fold, const TrackPublish* pub, hipStream_t s) {
   (void)iters;
   (void)chunk_id;
   if (nparts < 1 || nparts > 256) return hipErrorInvalidValue;  // <= 32 blocks per XCD shard (the shard-last loads)
+  if (!fold && pub->mirror != nullptr) return hipErrorInvalidValue;
   if (fold)
-    hipLaunchKernelGGL(m3s::gn_loop_kernel<true>, dim3(nparts), dim3(GN_THREADS), 0, s, *a, *p);
+    hipLaunchKernelGGL(m3s::gn_loop_kernel<true>, dim3(nparts), dim3(GN_THREADS), 0, s, *a, *p, *pub);
   else
-    hipLaunchKernelGGL(m3s::gn_loop_kernel<false>, dim3(nparts), dim3(GN_THREADS), 0, s, *a, *p);
+    hipLaunchKernelGGL(m3s::gn_loop_kernel<false>, dim3(nparts), dim3(GN_THREADS), 0, s, *a, *p, *pub);
   return hipGetLastError();
 }
 

@@ -42,10 +42,15 @@ def _depth(u, v, H, W, g):
 
 def _smooth_desc(H, W, Fd, g, sigma=2.0):
     n = torch.randn(1, Fd, H, W, generator=g)
-    r = int(3 * sigma)
-    k = torch.exp(-0.5 * (torch.arange(-r, r + 1, dtype=torch.float32) / sigma) ** 2)
-    k = k / k.sum()
+
+    def kernel(size):  # reflect padding needs a radius below the image size: images under 7 pixels get a shorter one
+        r = min(int(3 * sigma), size - 1)
+        k = torch.exp(-0.5 * (torch.arange(-r, r + 1, dtype=torch.float32) / sigma) ** 2)
+        return r, k / k.sum()
+
+    r, k = kernel(W)
     n = F.conv2d(F.pad(n, (r, r, 0, 0), mode="reflect"), k.view(1, 1, 1, -1).repeat(Fd, 1, 1, 1), groups=Fd)
+    r, k = kernel(H)
     n = F.conv2d(F.pad(n, (0, 0, r, r), mode="reflect"), k.view(1, 1, -1, 1).repeat(Fd, 1, 1, 1), groups=Fd)
     return F.normalize(n[0].permute(1, 2, 0), dim=-1)  # (H, W, F)
 
