@@ -38,7 +38,9 @@ const char* m3s_last_error(void);
 /* Per-kernel HIP-event timing (no reference counterpart; the reference's profiler.py wraps regions
  * with torch.cuda.synchronize). When enabled, every launch group is bracketed by hipEvents on its
  * own stream under a name: prep_rays, proj_occlusion, refine_lin, track_setup, gn_iters,
- * ba_linearize, ba_solve. query synchronises the recorded events. */
+ * ba_linearize, ba_solve. query synchronises the recorded events. (m3s_match runs the projection
+ * search inside the refine launch where the tile path is taken: refine_lin then covers both and
+ * proj_occlusion has no spans, count 0; M3S_MATCH_FUSE_PROJ=0 separates them.) */
 void m3s_timing_enable(int on);
 void m3s_timing_reset(void);
 int m3s_timing_query(const char* name, double* total_ms, int* count);

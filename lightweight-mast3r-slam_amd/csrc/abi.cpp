@@ -32,6 +32,9 @@ hipError_t m3s_launch_refine_f16(const void*, const void*, const int64_t*, int64
                                  hipStream_t);
 hipError_t m3s_launch_refine_f32(const float*, const float*, const int64_t*, int64_t*, int, int, int, int, int, int,
                                  int, hipStream_t);
+hipError_t m3s_launch_refine_tile_proj(const void*, const float*, int64_t*, uint8_t*, const float*, const float*,
+                                       const float*, const int64_t*, int, int, int, int, int, int, int, float, float,
+                                       float, const float*, int, hipStream_t);
 hipError_t m3s_launch_refine_lin(const void*, const float*, const int*, int64_t*, int, int, int, int, int, int,
                                  void*, int*, const float*, hipStream_t);
 hipError_t m3s_launch_track_setup(const TrackArgs*, const TrackParams*, hipStream_t);
@@ -267,6 +270,27 @@ extern "C" int m3s_match(const float* X11, const float* X21, const float* D11, c
                             screen ? w.cpart : nullptr, s),
             "match prep launch");
   }
+  // every wave scores its window outliers in place (no deferred list, no refine_outlier_kernel launch: on coherent
+  // inputs the list is empty and the launch alone cost ~2 us per frame; a scattered warm start, every lane an
+  // outlier, costs its waves 64 pixels x 5 levels serially). M3S_REFINE_INPLACE=0: waves with more than
+  // RT_INPLACE_MAX outliers defer them to the list and the outlier launch
+  const char* inplace_env = getenv("M3S_REFINE_INPLACE");
+  const bool inplace = !(inplace_env != nullptr && inplace_env[0] == '0');
+  // the tile path runs the projection search inside the refine launch (refine.hip FUSE_PROJ: two launches per match,
+  // no p1 round trip; same idx / valid bit for bit). M3S_MATCH_FUSE_PROJ=0 (read per call so tests can compare both)
+  // restores the proj_occlusion launch, and so does the deferred list (M3S_REFINE_INPLACE=0): its counter is
+  // cleared by that launch
+  const char* fuse_env = getenv("M3S_MATCH_FUSE_PROJ");
+  const bool fuse = planar && inplace && !(fuse_env != nullptr && fuse_env[0] == '0') &&
+                    (size_t)9 * H * W < ((size_t)1 << 31);
+  if (fuse) {
+    Span sp("refine_lin", s);
+    HIP_TRY(m3s_launch_refine_tile_proj(D11h, D21, idx_out, valid_out, rays9, X11, X21, idx_init, B, H, W, F, radius,
+                                        dilation_max, max_iter, lambda_init, cost_thresh, dist_thresh,
+                                        screen ? w.cpart : nullptr, m3s_prep_parts(B, H, W), s),
+            "match fused proj + refine launch");
+    return M3S_OK;
+  }
   {
     Span sp("proj_occlusion", s);
     HIP_TRY(m3s_launch_proj_occlusion(rays9, X11, X21, idx_init, p1, valid_out, B, H, W, max_iter, lambda_init,
@@ -278,12 +302,6 @@ extern "C" int m3s_match(const float* X11, const float* X21, const float* D11, c
   // (matching.py:78-88); D11h is never read then.
   {
     Span sp("refine_lin", s);
-    // every wave scores its window outliers in place (no deferred list, no refine_outlier_kernel launch: on coherent
-    // inputs the list is empty and the launch alone cost ~2 us per frame; a scattered warm start, every lane an
-    // outlier, costs its waves 64 pixels x 5 levels serially). M3S_REFINE_INPLACE=0: waves with more than
-    // RT_INPLACE_MAX outliers defer them to the list and the outlier launch
-    const char* inplace_env = getenv("M3S_REFINE_INPLACE");
-    const bool inplace = !(inplace_env != nullptr && inplace_env[0] == '0');
     HIP_TRY(m3s_launch_refine_lin(D11h, D21, p1, idx_out, B, H, W, F, radius, radius > 0 ? dilation_max : 0,
                                   inplace ? nullptr : w.olist,
                                   w.ocount, screen ? w.cmax : nullptr, s),

@@ -27,12 +27,14 @@
 //     op path, no workspace) the wave scores its outliers in place, one at a time (wave_level).
 //   * Tiles are dealt to XCDs in contiguous runs (bijective remap) so each XCD's 4 MiB L2 holds
 //     its slab of D11.
+//   * On the fused match path the same launch first runs the projection search for the tile's pixels (FUSE_PROJ,
+//     m3s_proj.hpp): no launch and no p1 round trip between the LM search and the levels.
 // Compiled with -ffp-contract=off and -fno-slp-vectorize: each candidate's half sum stays a scalar chain (VOP2
 // v_add_f16 for the even channel, SDWA v_add_f16 for the odd one) instead of the SLP vectoriser pairing two
 // candidates per v_pk_add_f16 behind v_perm / v_pack transposes. Measured issue costs on gfx950 at 4 waves/SIMD
 // (scripts/micro/fma_rates, profiles/r03_valu_issue_rates.txt): VOP2 f16 add 1.18 ns, SDWA / VOP3P / v_perm
 // 2.03-2.09 ns per wave-instruction, so 2.67 ns per channel-candidate against 3.1 ns paired: 125 -> 116 us.
-#include "m3s_half.hpp"
+#include "m3s_proj.hpp"
 
 namespace m3s {
 
@@ -611,19 +613,55 @@ __device__ __forceinline__ void store_out(void* outv, size_t bn, int W, int cu, 
   }
 }
 
+// Where the FUSE_PROJ instance issues the six loads of its D21 row (vmcnt retires in order: once they are issued, the
+// wave's next wait on an LM gather waits for them too). 0: at kernel start; 1: staggered, block b behind LM iteration
+// 1 + b % RT_D21_K, so the 1024 resident blocks' 25 MB trickle in under the latency-bound LM phase; 2 (shipped):
+// behind the LM loop, their latency under the tile-flow exchange. The blocks leave the LM loop 16 to 31 us after the
+// launch starts, which spreads the loads by itself. Measured (profiles/match_fuse_proj_ab.json, alternating bench
+// runs on four boxes): 2 is the fastest and the steadiest, 1 within 1 us of it with slow runs, 0 slowest.
+#ifndef RT_D21_PLACE
+#define RT_D21_PLACE 2
+#endif
+#ifndef RT_D21_K
+#define RT_D21_K 8
+#endif
+
+// The projection search's arguments of the FUSE_PROJ instance (proj_occlusion_kernel's, matching.hip)
+struct ProjArgs {
+  const float* rays9;        // (B,H,W,9) prep_rays_kernel's ray image
+  const float* X11;          // (B,H,W,3) raw points of image 1 (occlusion gather)
+  const float* X21;          // (B,N,3) raw points of image 2
+  const int64_t* idx_init;   // (B,N) warm start, nullable (identity)
+  uint8_t* valid;            // (B,N) out
+  const float* cnorm_part;   // SCREEN: prep's tile partials of the descriptor-norm bound
+  int nparts, max_iter;
+  float lambda_init, cost_thresh, dist_thresh;
+};
+
 // P1_I64: p1 given as (B,N,2) int64 (reference op) else int32 (fused); LIN_OUT: write idx = u + W v.
 // SCREEN: bound-screened scoring (cmaxp = the descriptor-norm bound written by prep / proj_occlusion).
 // LIN_OUT (fused path) reads the PLANAR D11h of prep_rays_kernel.
+// FUSE_PROJ: the launch also runs the projection search (proj_occlusion_kernel's arithmetic in its order, from the
+// shared m3s_proj.hpp, so the centres and valid are bit-identical): each lane projects its own pixel, keeps the
+// centre in registers (no p1 traffic), writes valid and goes on into the levels; one wave per block reduces prep's
+// norm partials itself (no launch sits between prep and this one; the max is order-independent, so every block gets
+// the same bits). Runs without a deferred list only (olist == nullptr: nothing clears ocount in front of it).
 #ifndef RT_MIN_BLOCKS  // blocks per CU the register budget is sized for (16 waves: 128 VGPRs, the LDS limit too)
 #define RT_MIN_BLOCKS (16 / RT_WAVES)
 #endif
-template <bool D21_F32, bool P1_I64, bool LIN_OUT, bool SCREEN>
+template <bool D21_F32, bool P1_I64, bool LIN_OUT, bool SCREEN, bool FUSE_PROJ = false>
 __global__ void __launch_bounds__(RT_THREADS, RT_MIN_BLOCKS) refine_tile_kernel(const h1* __restrict__ D11h, const void* __restrict__ D21,
                                                              const void* __restrict__ p1v, void* __restrict__ outv,
                                                              int H, int W, int dilation_max, int tiles_x,
                                                              int tiles_per_img, int nblocks, int4* olist,
-                                                             int* ocount, const float* __restrict__ cmaxp) {
+                                                             int* ocount, const float* __restrict__ cmaxp,
+                                                             const ProjArgs pa) {
   constexpr int F = 24;
+  static_assert(!FUSE_PROJ || (D21_F32 && !P1_I64 && LIN_OUT), "the fused projection feeds the fused match path");
+#ifdef M3S_REFINE_BSTAMPS
+  const unsigned long long stamp_top = __builtin_amdgcn_s_memrealtime();
+  unsigned long long stamp_lm = 0;
+#endif
   __shared__ uint4 lds[RT_ROWS * RT_COLS];
   int(*s_red)[4] = reinterpret_cast<int(*)[4]>(&lds[0]);  // level-start reductions alias the window
   const int lb = xcd_remap(blockIdx.x, nblocks);
@@ -653,13 +691,64 @@ __global__ void __launch_bounds__(RT_THREADS, RT_MIN_BLOCKS) refine_tile_kernel(
   t.img = D11h + (size_t)b * N * F;
   h2 q[F / 2];
   int cu = 0, cv = 0;
-  if (active) {
+  float4 dv[F / 4];   // FUSE_PROJ: the raw D21 row, converted where it is first needed
+  float cmax_w = 0.0f;  // FUSE_PROJ && SCREEN: the descriptor-norm bound, held by wave 0 until the tile-flow exchange
+  if constexpr (FUSE_PROJ) {
+    // a lane past the image projects the nearest pixel inside it (every address stays in bounds, no branch join in
+    // front of the loads) and writes nothing
+    const int n = min(t.v_pix, H - 1) * W + min(t.u_pix, W - 1);
+    const size_t bnc = (size_t)b * N + n;
+    const float4* qsrc = reinterpret_cast<const float4*>(reinterpret_cast<const float*>(D21) + bnc * F);
+    auto issue_q = [&]() {
+#pragma unroll
+      for (int k = 0; k < F / 4; k++) dv[k] = qsrc[k];
+    };
+    if constexpr (RT_D21_PLACE == 0) issue_q();
+    const float x = pa.X21[bnc * 3 + 0], y = pa.X21[bnc * 3 + 1], z = pa.X21[bnc * 3 + 2];
+    const int64_t i0 = pa.idx_init != nullptr ? pa.idx_init[bnc] : (int64_t)n;
+    if constexpr (SCREEN) {
+      // reduce_cnorm's loads, in flight beside the pixel's own (4 KB from L2 at 512x512)
+      if (t.wid == 0) cmax_w = reduce_cnorm_wave(pa.cnorm_part, pa.nparts);
+    }
+    const float nrm = fmaxf(norm3_ref(x, y, z), 1e-12f);  // F.normalize (matching.py:44)
+    const float p[3] = {x / nrm, y / nrm, z / nrm};
+    float u, v;
+    lin_to_pixel_f(i0, W, u, v);
+    bool conv = false;
+    float Xg[3];  // X11 at the final pixel, gathered during the last LM iteration
+    // wave-uniform (scalar) test: a per-lane branch inside the LM loop is costly
+    const int slot = (int)(blockIdx.x % RT_D21_K);
+    auto after_iter = [&](int i) {
+      if constexpr (RT_D21_PLACE == 1) {
+        if (i == slot) issue_q();
+      }
+    };
+    iter_proj_point<true>(pa.rays9 + (size_t)b * N * 9, H, W, p, u, v, conv, pa.max_iter, pa.lambda_init,
+                          pa.cost_thresh, pa.X11 + (size_t)b * N * 3, Xg, after_iter);
+    if constexpr (RT_D21_PLACE == 2) issue_q();
+    cu = (int)u;  // .long() truncation; u, v >= 1 after clamping
+    cv = (int)v;
+    // (every lane: a branch here would leave Xg's gather pending in the lanes past the image, and the next write of
+    // its registers would drain the D21 loads with it)
+    const float dx = Xg[0] - x, dy = Xg[1] - y, dz = Xg[2] - z;
+    const float d = norm3_ref(dx, dy, dz);  // torch.linalg.norm (matching.py:71-73)
+    const uint8_t vbyte = conv && (d < pa.dist_thresh);
+    if (active) pa.valid[bn] = vbyte;
+    if constexpr (RT_D21_PLACE == 1) {
+      // fewer LM iterations than this block's slot: behind Xg's use, so its wait does not cover these loads
+      if (slot >= pa.max_iter - 1) issue_q();
+    }
+#ifdef M3S_REFINE_BSTAMPS
+    stamp_lm = __builtin_amdgcn_s_memrealtime();
+#endif
+  } else if (active) {
     load_query<F, D21_F32>(D21, bn, q);
     load_p1<P1_I64>(p1v, bn, cu, cv);
   } else {
 #pragma unroll
     for (int k = 0; k < F / 2; k++) q[k] = h2{(h1)0.0f, (h1)0.0f};
   }
+  float cmax_b = 0.0f;  // FUSE_PROJ && SCREEN: wave 0's cmax_w, for every wave
   {  // tile flow estimate, once per tile: the centres move by at most 3d per level, well inside the
      // +-16 px inlier band, so the initial mean serves every level (saves a block reduction per level)
     int su = active ? cu - t.u_pix : 0, sv = active ? cv - t.v_pix : 0, na = active ? 1 : 0;
@@ -673,8 +762,10 @@ __global__ void __launch_bounds__(RT_THREADS, RT_MIN_BLOCKS) refine_tile_kernel(
       s_red[t.wid][0] = su;
       s_red[t.wid][1] = sv;
       s_red[t.wid][2] = na;
+      if constexpr (FUSE_PROJ && SCREEN) s_red[t.wid][3] = __float_as_int(cmax_w);
     }
     __syncthreads();
+    if constexpr (FUSE_PROJ && SCREEN) cmax_b = __int_as_float(__builtin_amdgcn_readfirstlane(s_red[0][3]));
     // block-uniform: SGPRs (readfirstlane), not VGPRs live across every level
     int tu = 0, tv = 0, tn = 0;
 #pragma unroll
@@ -689,19 +780,32 @@ __global__ void __launch_bounds__(RT_THREADS, RT_MIN_BLOCKS) refine_tile_kernel(
     t.tcu = tx * RT_TW + RT_TW / 2 + t.fu;
     t.tcv = ty * RT_TH + RT_TH / 2 + t.fv;
   }
+  if constexpr (FUSE_PROJ) {
+    // the D21 row, f32 -> f16 (RNE, == torch .half(): load_query's conversion) behind the tile-flow exchange: the
+    // loads' latency runs under it
+#pragma unroll
+    for (int k = 0; k < F / 4; k++) {
+      q[2 * k + 0] = h2{(h1)dv[k].x, (h1)dv[k].y};
+      q[2 * k + 1] = h2{(h1)dv[k].z, (h1)dv[k].w};
+    }
+  }
   t.bq = 0.0f;
   t.sok = false;
   if constexpr (SCREEN) {
     float qq = 0.0f;
 #pragma unroll
     for (int k = 0; k < F / 2; k++) qq = __builtin_amdgcn_fdot2(q[k], q[k], qq, false);
-    const float pq = sqrtf(qq) * *cmaxp * 1.001f;  // |q|_2 |c|_2 bound, rounded up
+    float cm;
+    if constexpr (FUSE_PROJ) cm = cmax_b; else cm = *cmaxp;
+    const float pq = sqrtf(qq) * cm * 1.001f;  // |q|_2 |c|_2 bound, rounded up
     t.sok = pq <= 16384.0f;                         // false for NaN / inf
     t.bq = t.sok ? 0.0125f * pq + 0x1p-18f : 0.0f;
   }
   const bool mine = active;  // deferred pixels are written by refine_outlier_kernel
 #ifdef M3S_REFINE_BSTAMPS
-  if (threadIdx.x == 0 && blockIdx.x < 8192) g_refine_bstamps[blockIdx.x * 4 + 0] = __builtin_amdgcn_s_memrealtime();
+  // the unfused instance: the levels' start; FUSE_PROJ: the kernel's first instruction (the LM phase's end: slot 3)
+  if (threadIdx.x == 0 && blockIdx.x < 8192)
+    g_refine_bstamps[blockIdx.x * 4 + 0] = FUSE_PROJ ? stamp_top : __builtin_amdgcn_s_memrealtime();
 #endif
   h1 max_score = (h1)0.0f;   // numeric_limits<c10::Half>::min() == +0, never reset between levels
   // the levels as straight-line code (d = dilation_max .. 1) instead of a loop over a switch of the eight inlined level
@@ -736,7 +840,7 @@ __global__ void __launch_bounds__(RT_THREADS, RT_MIN_BLOCKS) refine_tile_kernel(
     g_refine_bstamps[blockIdx.x * 4 + 2] = hw;
     unsigned long long na = 0;
     for (int w = 0; w < RT_WAVES; w++) na += s_act[w];
-    g_refine_bstamps[blockIdx.x * 4 + 3] = na;
+    g_refine_bstamps[blockIdx.x * 4 + 3] = FUSE_PROJ ? stamp_lm : na;  // FUSE_PROJ: when the LM phase ended
   }
 #endif
 }
@@ -803,13 +907,13 @@ extern "C" hipError_t m3s_launch_refine_tile(const void* D11h, const void* D21, 
   if (ol == nullptr) ocount = nullptr;
   if (fused && cmax != nullptr)
     hipLaunchKernelGGL((m3s::refine_tile_kernel<true, false, true, true>), dim3(nb), dim3(RT_THREADS), 0, s, a, D21, p1,
-                       out, H, W, dilation_max, tx, tx * ty, nb, ol, ocount, cmax);
+                       out, H, W, dilation_max, tx, tx * ty, nb, ol, ocount, cmax, m3s::ProjArgs{});
   else if (fused)
     hipLaunchKernelGGL((m3s::refine_tile_kernel<true, false, true, false>), dim3(nb), dim3(RT_THREADS), 0, s, a, D21, p1,
-                       out, H, W, dilation_max, tx, tx * ty, nb, ol, ocount, nullptr);
+                       out, H, W, dilation_max, tx, tx * ty, nb, ol, ocount, nullptr, m3s::ProjArgs{});
   else
     hipLaunchKernelGGL((m3s::refine_tile_kernel<false, true, false, false>), dim3(nb), dim3(RT_THREADS), 0, s, a, D21,
-                       p1, out, H, W, dilation_max, tx, tx * ty, nb, ol, ocount, nullptr);
+                       p1, out, H, W, dilation_max, tx, tx * ty, nb, ol, ocount, nullptr, m3s::ProjArgs{});
   if (ol != nullptr) {
     // 1024 waves: the list is empty or short once waves score up to RT_INPLACE_MAX outliers in place (a smaller
     // grid launches and drains faster); pathological inputs (every lane an outlier) take several passes
@@ -821,6 +925,33 @@ extern "C" hipError_t m3s_launch_refine_tile(const void* D11h, const void* D21, 
       hipLaunchKernelGGL((m3s::refine_outlier_kernel<false, false>), dim3(ob), dim3(256), 0, s, a, D21, out, H, W,
                          ol, ocount);
   }
+  return hipGetLastError();
+}
+
+// The fused match path's tile launch with the projection search inside (refine_tile_kernel FUSE_PROJ): X21 /
+// idx_init (nullable) -> valid and idx, no p1 buffer, no deferred list. cnorm_part (nullable: unscreened scoring):
+// prep's nparts tile partials. hipErrorNotSupported when the shape is not eligible (the caller takes the
+// proj_occlusion + refine launches).
+extern "C" hipError_t m3s_launch_refine_tile_proj(const void* D11h, const float* D21, int64_t* idx_out, uint8_t* valid,
+                                                  const float* rays9, const float* X11, const float* X21,
+                                                  const int64_t* idx_init, int B, int H, int W, int F, int radius,
+                                                  int dilation_max, int max_iter, float lambda_init, float cost_thresh,
+                                                  float dist_thresh, const float* cnorm_part, int nparts,
+                                                  hipStream_t s) {
+  if (!m3s_refine_tile_ok(B, H, W, F, radius, dilation_max)) return hipErrorNotSupported;
+  if ((size_t)9 * H * W >= ((size_t)1 << 31)) return hipErrorNotSupported;  // bilin_sample9's 32-bit offsets
+  const int tx = (W + RT_TW - 1) / RT_TW, ty = (H + RT_TH - 1) / RT_TH, nb = tx * ty * B;
+  const m3s::h1* a = reinterpret_cast<const m3s::h1*>(D11h);
+  const m3s::ProjArgs pa{rays9, X11, X21, idx_init, valid, cnorm_part, nparts, max_iter, lambda_init, cost_thresh,
+                         dist_thresh};
+  if (cnorm_part != nullptr)
+    hipLaunchKernelGGL((m3s::refine_tile_kernel<true, false, true, true, true>), dim3(nb), dim3(RT_THREADS), 0, s, a,
+                       (const void*)D21, (const void*)nullptr, (void*)idx_out, H, W, dilation_max, tx, tx * ty, nb,
+                       (int4*)nullptr, (int*)nullptr, (const float*)nullptr, pa);
+  else
+    hipLaunchKernelGGL((m3s::refine_tile_kernel<true, false, true, false, true>), dim3(nb), dim3(RT_THREADS), 0, s, a,
+                       (const void*)D21, (const void*)nullptr, (void*)idx_out, H, W, dilation_max, tx, tx * ty, nb,
+                       (int4*)nullptr, (int*)nullptr, (const float*)nullptr, pa);
   return hipGetLastError();
 }
 

@@ -3,6 +3,8 @@ import ctypes
 import os
 import sys
 
+# the unfused refine launch: the fused instance's stamps (kernel start, LM phase end) are read by refine_fuse_stamps.py
+os.environ.setdefault("M3S_MATCH_FUSE_PROJ", "0")
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 sys.path.insert(0, os.path.join(REPO, "lightweight-mast3r-slam_amd"))
