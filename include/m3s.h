@@ -22,7 +22,7 @@
 extern "C" {
 #endif
 
-#define M3S_ABI_VERSION 5
+#define M3S_ABI_VERSION 6
 
 #define M3S_OK 0
 #define M3S_EINVAL -1  /* bad shape / argument (reference: TORCH_CHECK -> RuntimeError) */
@@ -71,9 +71,15 @@ int m3s_refine_matches(int dtype, const void* D11, const void* D21, const int64_
  * Twc (Kp,8) f32 is updated IN PLACE (as the reference). Xs (Kp,N,3), Cs (Kp,N) f32; ii, jj (E) i64
  * global keyframe ids (remapped to dense ranks internally, gn_kernels.cu:161-170); idx (E,N) i64;
  * valid (E,N) u8; Q (E,N) f32. dx_out ((Kp-1),7) f32 receives the last step. iters_out (host,
- * nullable) receives the iteration count. The workspace must hold m3s_ba_workspace_size() bytes. */
+ * nullable) receives the iteration count. The workspace must hold m3s_ba_workspace_size() bytes.
+ * mode 3 (M3S_BA_MODE_CALIB_RAW): the residuals and results of mode 2 on constrain_points_to_ray(points)
+ * (geometry.py:37-42, global_opt.py:176), with the points in Xs / the keyframe table NOT constrained: the kernels
+ * read only the depth z of a point and form the target point X_j = (z x_of_u[u], z y_of_v[v], z) of pixel (u, v)
+ * from the plan's ray tables (m3s_ba_calib_rays), so a caller passes the keyframes' raw X_canon and makes no
+ * constrained copy. Same checks as mode 2: N == height * width, height and width below 65536. */
+#define M3S_BA_MODE_CALIB_RAW 3
 typedef struct m3s_ba_config {
-  int mode;          /* 0 points, 1 rays, 2 calib */
+  int mode;          /* 0 points, 1 rays, 2 calib (points on their pixel rays), 3 M3S_BA_MODE_CALIB_RAW */
   float sigma_a;     /* sigma_point | sigma_ray | sigma_pixel */
   float sigma_b;     /* -           | sigma_dist | sigma_depth */
   float C_thresh, Q_thresh;
@@ -104,7 +110,9 @@ int m3s_ba_make_plan(const m3s_ba_config* cfg, float* Twc, const float* Xs, cons
  * FactorGraph.get_poses_points builds with torch.stack (global_opt.py:114-121), the keyframes' own buffers.
  * Host arrays of Kp entries: X[k] -> that keyframe's (N,3) X_canon, C[k] -> its (N) confidence sum (device
  * pointers), N_avg[k] = its fusion count N; the average confidence is C * float32(1/N), exactly
- * Frame.get_average_conf (frame.py:93-94) on a torch device. Same plan and results as m3s_ba_make_plan. */
+ * Frame.get_average_conf (frame.py:93-94) on a torch device. Same plan and results as m3s_ba_make_plan.
+ * In every mode: rays (solve_GN_rays) and, with mode 3, calib (solve_GN_calib), whose stacked path otherwise
+ * copies the points twice (torch.stack, then constrain_points_to_ray) before each solve. */
 typedef struct m3s_ba_keyframes {
   const float* const* X;
   const float* const* C;
@@ -163,6 +171,10 @@ int m3s_ba_plan_info(const m3s_ba_plan* plan, int* info);
  * (source level, target column), [3] = update sources, [4] = source-map entries, [5] = groups run by
  * factor tasks. */
 int m3s_ba_pattern_stats(const int64_t* ii, const int64_t* jj, int E, int Kp, int* stats);
+/* Host-only: the pixel-ray tables a mode-3 plan builds for cfg (fx, fy, cx, cy, width, height; host arrays of width
+ * and height floats): x_of_u[u] = (float(u) - cx) / fx, y_of_v[v] = (float(v) - cy) / fy, each one fp32 subtraction
+ * then one correctly rounded fp32 division (geometry.backproject's operation order; not a reciprocal-multiply). */
+int m3s_ba_calib_rays(const m3s_ba_config* cfg, float* x_of_u, float* y_of_v);
 
 /* ---------------------------------------------------------------------------------------------
  * Fused operators (replace stretches of the reference's Python glue)

@@ -577,6 +577,23 @@ int ba_chunks(int N, int E) {
   return std::max(base, std::min(most, (BA_LIN_MIN_BLOCKS + E - 1) / E));
 }
 
+// The pixel-ray tables of raw calib (m3s_ba_calib_rays): x_of_u[u] = (float(u) - cx) / fx, y_of_v[v] = (float(v) - cy)
+// / fy, each one fp32 subtraction then one correctly rounded fp32 division: geometry.backproject's operation order on a
+// torch device with K on that device, so z * table entry is constrain_points_to_ray's value bit for bit. The volatile
+// intermediates pin that order: no reciprocal-multiply, no fused or widened evaluation whatever the host flags.
+void ba_calib_rays(const m3s_ba_config* cfg, float* x_of_u, float* y_of_v) {
+  for (int u = 0; u < cfg->width; u++) {
+    volatile float d = (float)u - cfg->cx;
+    volatile float q = d / cfg->fx;
+    x_of_u[u] = q;
+  }
+  for (int v = 0; v < cfg->height; v++) {
+    volatile float d = (float)v - cfg->cy;
+    volatile float q = d / cfg->fy;
+    y_of_v[v] = q;
+  }
+}
+
 constexpr int BA_DENSE_MAX_POSES = 1025;  // dense fallback workspace: (2n+1) n doubles, ~0.8 GB at this size
 
 // factor blocks of the densest possible pattern (every pose coupled to every other)
@@ -589,14 +606,16 @@ inline size_t ba_max_blocks(int Kp) {
 // symbolic factorisation (ba_pattern.h), packed at their actual sizes into a region sized for the worst case
 constexpr int BA_SYM_SECTIONS = 16;  // the symbolic half's sections (build_symbolic)
 constexpr int BA_SP_PLAN_BYTES = 144 * 1024;  // ba.hip SP_PLAN_BYTES: LDS of the one-workgroup factor kernel
-constexpr int BA_BLOB_SECTIONS = 8 + BA_SYM_SECTIONS;
+constexpr int BA_BLOB_SECTIONS = 9 + BA_SYM_SECTIONS;
+// floats of the raw-calib pixel-ray tables (W + H with W H = N, so at most N + 1; W, H < 65536)
+inline size_t ba_ray_tab_floats(int N) { return std::min<size_t>((size_t)N + 1, 2 * 65535); }
 // update pairs (source block row -> target block) the plan can hold: every pattern up to K ~ 600, and the
 // sparse patterns of larger graphs
 inline size_t ba_max_pairs(int Kp) {
   const size_t nb = (size_t)std::max(0, Kp - 1);
   return std::min(nb * nb * nb / 6 + nb * nb + 64, 32 * ba_max_blocks(Kp) + 64);
 }
-size_t ba_blob_capacity(int Kp, int E, int chunks) {
+size_t ba_blob_capacity(int Kp, int N, int E, int chunks) {
   const size_t nb = (size_t)std::max(0, Kp - 1), nLm = ba_max_blocks(Kp);
   // ranks, perm, col_ptr, rowL, lev_ptr, lev_col, grp_ptr, grp, pull_grp, src, sidx, asm CSR, rhs CSR
   const size_t ints = 2 * (size_t)E + nb + (nb + 1) + nLm + (nb + 1) + nb + (nb + 2) + 4 * nLm + nb + 4 * nLm +
@@ -605,7 +624,7 @@ size_t ba_blob_capacity(int Kp, int E, int chunks) {
                       2 * (size_t)E +       // + record slots and the pack list (record reuse)
                       8 * 2 * nb * (size_t)std::min<size_t>(BA_MAX_WIDE_STEPS, nb + 1) +  // + wide-step task records
                       2 * (M3S_BA_SP_WAVES + 1) + 2 * nb + 2 * (nb + nLm);  // + the dataflow schedule
-  return ints * 4 + (size_t)Kp * (8 + 8 + 4) + BA_BLOB_SECTIONS * 16;
+  return ints * 4 + (size_t)Kp * (8 + 8 + 4) + ba_ray_tab_floats(N) * 4 + BA_BLOB_SECTIONS * 16;
 }
 
 size_t ba_carve(Carver& c, int Kp, int N, int E, int chunks, BaArgs* a, size_t* es_off, void** blob) {
@@ -625,7 +644,7 @@ size_t ba_carve(Carver& c, int Kp, int N, int E, int chunks, BaArgs* a, size_t* 
   a->info = c.take<int>(8);
   a->done = a->info + 1;
   a->iters = a->info + 2;
-  *blob = c.take<char>(ba_blob_capacity(Kp, E, chunks));
+  *blob = c.take<char>(ba_blob_capacity(Kp, N, E, chunks));
   return c.off;
 }
 
@@ -726,6 +745,14 @@ extern "C" int m3s_ba_pattern_stats(const int64_t* ii, const int64_t* jj, int E,
   stats[3] = (int)P.src.size() / 4;
   stats[4] = (int)P.sidx.size();
   stats[5] = (int)std::count_if(P.pull_grp.begin(), P.pull_grp.end(), [](int g) { return g >= 0; });
+  return M3S_OK;
+}
+
+extern "C" int m3s_ba_calib_rays(const m3s_ba_config* cfg, float* x_of_u, float* y_of_v) {
+  M3S_CHECK(cfg && x_of_u && y_of_v, "ba calib rays: null argument");
+  M3S_CHECK(cfg->width > 0 && cfg->height > 0 && cfg->width < 65536 && cfg->height < 65536,
+            "ba calib rays: width and height must be in [1, 65535]");
+  ba_calib_rays(cfg, x_of_u, y_of_v);
   return M3S_OK;
 }
 
@@ -955,15 +982,18 @@ int ba_make_plan_impl(const m3s_ba_config* cfg, float* Twc, const float* const* 
                       const int64_t* edge_uid, const int64_t* kf_uid, void* workspace, size_t workspace_bytes,
                       m3s_ba_plan* plan, void* stream) {
   M3S_CHECK(cfg && plan, "ba: null argument");
-  M3S_CHECK(cfg->mode >= 0 && cfg->mode <= 2, "ba: mode must be 0 (points), 1 (rays) or 2 (calib)");
+  M3S_CHECK(cfg->mode >= 0 && cfg->mode <= M3S_BA_MODE_CALIB_RAW,
+            "ba: mode must be 0 (points), 1 (rays), 2 (calib) or 3 (calib, raw points)");
+  static_assert(M3S_BA_MODE_CALIB_RAW == BA_MODE_CALIB_RAW, "m3s.h and m3s_ba.h name the same mode");
+  const bool calib = cfg->mode == BA_MODE_CALIB || cfg->mode == BA_MODE_CALIB_RAW;
   M3S_CHECK(Kp >= 1 && N >= 1 && E >= 0, "ba: bad sizes");
   M3S_CHECK(0 <= e0 && e0 <= e1 && e1 <= E, "ba: bad shard range");
   // the workspace reserves the factor and plan tables of the densest pattern (m3s_ba_workspace_size knows no
   // edges): nb(nb+1)/2 blocks of 512 B, 4.3 GB at this cap
   M3S_CHECK(Kp <= M3S_BA_MAX_POSES, "ba: at most 4096 poses (M3S_BA_MAX_POSES)");
-  if (cfg->mode == 2) M3S_CHECK(cfg->width > 0 && cfg->height > 0 && (int64_t)cfg->width * cfg->height == N,
-                                "ba calib: height*width must equal the points per keyframe");
-  if (cfg->mode == 2)  // the 12-B calib record holds the matched pixel as u | v << 16 (ba.hip pack_record)
+  if (calib) M3S_CHECK(cfg->width > 0 && cfg->height > 0 && (int64_t)cfg->width * cfg->height == N,
+                       "ba calib: height*width must equal the points per keyframe");
+  if (calib)  // the 12-B calib record holds the matched pixel as u | v << 16 (ba.hip pack_record)
     M3S_CHECK(cfg->width < 65536 && cfg->height < 65536, "ba calib: width and height must be below 65536");
   if (workspace_bytes < m3s_ba_workspace_size(Kp, N, E)) return fail(M3S_ESPACE, "ba: workspace too small");
   hipStream_t s = (hipStream_t)stream;
@@ -1002,7 +1032,7 @@ int ba_make_plan_impl(const m3s_ba_config* cfg, float* Twc, const float* const* 
   if (RC) {
     const bool same = RC->valid && RC->N == N && RC->mode == cfg->mode && RC->Q_thresh == cfg->Q_thresh &&
                       RC->C_thresh == cfg->C_thresh &&
-                      (cfg->mode != 2 || (RC->W == cfg->width && RC->z_eps == cfg->z_eps));
+                      (!calib || (RC->W == cfg->width && RC->z_eps == cfg->z_eps));
     if (!same) {
       RC->reset_maps();
       RC->N = N;
@@ -1163,6 +1193,12 @@ int ba_make_plan_impl(const m3s_ba_config* cfg, float* Twc, const float* const* 
     size_t bytes;
     const void** dst;
   };
+  // raw calib: the pixel-ray tables the linearisation builds X_j from (x_of_u then y_of_v, W + H floats)
+  std::vector<float> ray_tab;
+  if (cfg->mode == BA_MODE_CALIB_RAW) {
+    ray_tab.resize((size_t)cfg->width + cfg->height);
+    ba_calib_rays(cfg, ray_tab.data(), ray_tab.data() + cfg->width);
+  }
   const Sec secs[] = {
       {ri.data() + e0, sizeof(int) * (e1 - e0), (const void**)&P.a.ii_rank},
       {rj.data() + e0, sizeof(int) * (e1 - e0), (const void**)&P.a.jj_rank},
@@ -1172,11 +1208,12 @@ int ba_make_plan_impl(const m3s_ba_config* cfg, float* Twc, const float* const* 
       {lin_tab.data(), sizeof(int) * lin_tab.size(), (const void**)&P.a.lin_tab},
       {slot.data(), sizeof(int) * slot.size(), (const void**)&P.a.rec_slot},
       {pack.data(), sizeof(int) * pack.size(), (const void**)&P.a.pack_list},
+      {ray_tab.data(), sizeof(float) * ray_tab.size(), (const void**)&P.a.ray_tab},
   };
   static_assert(sizeof(secs) / sizeof(secs[0]) + BA_SYM_SECTIONS == BA_BLOB_SECTIONS, "blob sections");
   size_t total = 0;
   for (const Sec& x : secs) total += (x.bytes + 15) & ~(size_t)15;
-  const size_t capacity = ba_blob_capacity(Kp, E, chunks);
+  const size_t capacity = ba_blob_capacity(Kp, N, E, chunks);
   if (total > capacity) return fail(M3S_EINVAL, "ba: plan tables exceed the workspace blob");
   {
     PlanStage& st = plan_stage();
@@ -1202,6 +1239,7 @@ int ba_make_plan_impl(const m3s_ba_config* cfg, float* Twc, const float* const* 
     HIP_TRY(hipEventRecord(st.landed, s), "ba stage record");
     st.pending = true;
   }
+  if (ray_tab.empty()) P.a.ray_tab = nullptr;
   if (!RC) P.a.rec_slot = nullptr;  // every edge packs into its own slot (the pack list is the source-keyframe order)
   Y->dst = static_cast<char*>(blob) + total;
   HIP_TRY(hipMemsetAsync(P.a.info, 0, 8 * sizeof(int), s), "ba memset");

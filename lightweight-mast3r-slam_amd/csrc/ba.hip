@@ -31,6 +31,11 @@ namespace m3s {
 
 #define BA_NSUM 36
 
+// the two calib modes share the record format, the pack and the rows; they differ only in how the linearisation forms
+// X_j: read whole (BA_MODE_CALIB: the caller constrained the points to their pixel rays) or built from the raw
+// point's depth and the plan's ray tables (BA_MODE_CALIB_RAW)
+constexpr bool ba_is_calib(int mode) { return mode == BA_MODE_CALIB || mode == BA_MODE_CALIB_RAW; }
+
 // ------------------------------------------------------------------------------------------
 // linearisation
 // ------------------------------------------------------------------------------------------
@@ -188,7 +193,7 @@ __device__ __forceinline__ float4 pack_finish(const BaParams& p, const float* Xi
                                               float* n) {
   // hardware sqrt (<= 1 ulp): parity is checked against the fp64 truth (1e-5)
   const float sw = valid ? __builtin_amdgcn_sqrtf(q) : 0.0f;
-  if constexpr (MODE == BA_MODE_CALIB) {
+  if constexpr (ba_is_calib(MODE)) {
     const int ind32 = (int)ind;  // < H*W < 2^31: 32-bit division
     const unsigned v_t = (unsigned)(ind32 / p.W), u_t = (unsigned)ind32 - v_t * (unsigned)p.W;  // W, H < 2^16 (plan)
     // log z_i once per call (the same __logf the linearisation applied every iteration), NaN marks z_i <= z_eps
@@ -224,7 +229,7 @@ __device__ __forceinline__ float4 pack_record(const BaArgs& a, const BaParams& p
 // a record as stored (pack_record) -> as computed on: calib {u_t, v_t, log z_i, sw} (exact: integers < 2^16)
 template <int MODE>
 __device__ __forceinline__ float4 rec_expand(float4 r) {
-  if constexpr (MODE == BA_MODE_CALIB) {
+  if constexpr (ba_is_calib(MODE)) {
     const unsigned uv = __builtin_bit_cast(unsigned, r.x);
     return make_float4((float)(uv & 0xffffu), (float)(uv >> 16), r.y, r.z);
   } else {
@@ -235,7 +240,7 @@ template <int MODE>
 __device__ __forceinline__ void rec_store(float4* slot, int k, float4 r) {
   // records: streamed out once per call (non-temporal under BA_PACK_NT, like the pack's input streams)
 #if BA_PACK_NT
-  if constexpr (MODE == BA_MODE_CALIB) {
+  if constexpr (ba_is_calib(MODE)) {
     // three 4-B stores, 12 B by construction: a vec3 store may legally be widened to 16 B, which would overwrite the
     // next record's first word (the backend merges these into one dwordx3)
     float* d = reinterpret_cast<float*>(slot) + 3 * (size_t)k;
@@ -247,13 +252,13 @@ __device__ __forceinline__ void rec_store(float4* slot, int k, float4 r) {
     __builtin_nontemporal_store(f4v{r.x, r.y, r.z, r.w}, reinterpret_cast<f4v*>(slot + k));
   }
 #else
-  if constexpr (MODE == BA_MODE_CALIB) reinterpret_cast<float3*>(slot)[k] = make_float3(r.x, r.y, r.z);
+  if constexpr (ba_is_calib(MODE)) reinterpret_cast<float3*>(slot)[k] = make_float3(r.x, r.y, r.z);
   else slot[k] = r;
 #endif
 }
 template <int MODE>
 __device__ __forceinline__ float4 rec_load(const float4* slot, int k) {
-  if constexpr (MODE == BA_MODE_CALIB) {
+  if constexpr (ba_is_calib(MODE)) {
     const float3 c = reinterpret_cast<const float3*>(slot)[k];
     return make_float4(c.x, c.y, c.z, 0.0f);
   } else {
@@ -312,8 +317,12 @@ __global__ void __launch_bounds__(256) ba_pack_kernel(BaArgs a, BaParams p, int 
 #pragma unroll
     for (int u = 0; u < U; u++) {
       ind[u] = vm[u] ? id[u] : 0;  // gn_kernels.cu reads index 0 for an invalid match
-      X[u][0] = Xi[(size_t)ind[u] * 3];
-      X[u][1] = Xi[(size_t)ind[u] * 3 + 1];
+      if constexpr (MODE == BA_MODE_CALIB_RAW) {
+        X[u][0] = X[u][1] = 0.0f;  // the calib record holds only log z_i: x_i, y_i (off the pixel ray here) are not read
+      } else {
+        X[u][0] = Xi[(size_t)ind[u] * 3];
+        X[u][1] = Xi[(size_t)ind[u] * 3 + 1];
+      }
       X[u][2] = Xi[(size_t)ind[u] * 3 + 2];
       ci[u] = Ci[ind[u]];
     }
@@ -365,10 +374,25 @@ __global__ void __launch_bounds__(256) ba_kf_compare_kernel(const BaKfCopy* __re
   if (__any(diff) && (threadIdx.x & 63) == 0) dirty[k] = 1;
 }
 
+// raw calib: LDS room for the plan's pixel-ray tables (x_of_u then y_of_v); only the raw-calib instances allocate it
+#ifndef BA_RAY_LDS
+#define BA_RAY_LDS 2048  // floats: 8 KB on top of the 38 KB of the flush, three blocks per CU still fit its 160 KB
+#endif
+template <bool ON>
+__device__ __forceinline__ float* ray_lds() {
+  if constexpr (ON) {
+    __shared__ float s_ray[BA_RAY_LDS];
+    return s_ray;
+  } else {
+    return nullptr;
+  }
+}
+
 // PACK: the first GN iteration of a call that packs every edge builds each point's record itself (pack_record, the
 // same values) and stores it for the later iterations: the pack's gathers (HBM-bound) run under this kernel's
 // VALU-bound rows instead of as a separate launch before it.
-template <int MODE, bool PACK>  // specialised per residual type: one mode's registers, not the union of three
+// RAYLDS (raw calib only): the pixel-ray tables fit BA_RAY_LDS and are read from LDS (else through the cache)
+template <int MODE, bool PACK, bool RAYLDS = false>  // specialised per residual type: one mode's registers, not the union of three
 __global__ void __launch_bounds__(256, BA_LIN_WAVES) ba_lin_kernel(BaArgs a, BaParams p) {
   if (*a.done) return;
   // the plan's block table: edges grouped by target keyframe, consecutive blocks on one XCD (xcd_remap)
@@ -427,6 +451,62 @@ __global__ void __launch_bounds__(256, BA_LIN_WAVES) ba_lin_kernel(BaArgs a, BaP
   const int per = (N + p.chunks - 1) / p.chunks;
   const int k_begin = chunk * per;
   const int k_end = min(N, k_begin + per);
+  // raw calib: X_j = (z_j x_of_u[u], z_j y_of_v[v], z_j) from the raw point's depth and the plan's ray tables (the
+  // values of constrain_points_to_ray: one rounded product per component, z_j * 1 exact). (pu, pv) is the pixel of this
+  // lane's first point of the coming round, k00 + threadIdx.x: one division per lane here, then a round adds the
+  // block-uniform (su, sv) = (stride % W, stride / W) with one wrap test; the second point sits (hu, hv) further.
+  // pix_next hands out the table entries of the round's two points and steps to the next round; it is called once per
+  // round, in round order. A lane past the chunk's end (its rows are skipped) may walk past the last image row: its v
+  // is clamped so that the table loads stay inside the tables.
+  // z_j is loaded through a global-memory pointer: a pointer read from the keyframe table is generic to the compiler,
+  // and a flat load counts against the LDS / scalar-memory counter too, which returns out of order: the wait for this
+  // round's z_j then also waited for the next round's prefetch issued just before it (the whole latency, every round)
+  typedef const float __attribute__((address_space(1))) * gfloat_p;
+  const gfloat_p Zj_base = (gfloat_p)(Xj_base + 2);
+  // RAYLDS: the block first copies the tables into LDS (the launcher picks this instance when W + H <= BA_RAY_LDS
+  // floats: every configured size): the per-round look-ups are then LDS reads, which leave the vector-memory pipe to
+  // the record and z_j streams; larger images read the tables through the cache.
+  int pu = 0, pv = 0, su = 0, sv = 0, hu = 0, hv = 0;
+  float* const s_ray = ray_lds<RAYLDS>();
+  if constexpr (MODE == BA_MODE_CALIB_RAW) {
+    const int W = p.W, kk = k_begin + (int)threadIdx.x, half = (int)blockDim.x;
+    if constexpr (RAYLDS) {
+      for (int i = (int)threadIdx.x; i < W + p.H; i += half) s_ray[i] = a.ray_tab[i];
+      __syncthreads();
+    }
+    pv = kk / W;
+    pu = kk - pv * W;
+    hv = half / W;
+    hu = half - hv * W;
+    sv = (2 * half) / W;
+    su = 2 * half - sv * W;
+  }
+  auto pix_next = [&](bool has1, f2& xu, f2& yv) {
+    const int W = p.W, vmax = p.H - 1;
+    int u1 = pu + hu, v1 = pv + hv;
+    if (u1 >= W) {
+      u1 -= W;
+      v1++;
+    }
+    if (!has1) {  // the missing second point repeats the first (rows)
+      u1 = pu;
+      v1 = pv;
+    }
+    const int i0 = W + min(pv, vmax), i1 = W + min(v1, vmax);
+    if constexpr (RAYLDS) {
+      xu = f2{s_ray[pu], s_ray[u1]};
+      yv = f2{s_ray[i0], s_ray[i1]};
+    } else {
+      xu = f2{a.ray_tab[pu], a.ray_tab[u1]};
+      yv = f2{a.ray_tab[i0], a.ray_tab[i1]};
+    }
+    pu += su;
+    pv += sv;
+    if (pu >= W) {
+      pu -= W;
+      pv++;
+    }
+  };
   f2 fL[28], fv[7];  // fp32 run sums, one slot per point of the pair
 #pragma unroll
   for (int c = 0; c < 28; c++) fL[c] = f2{0.0f, 0.0f};
@@ -560,6 +640,8 @@ __global__ void __launch_bounds__(256, BA_LIN_WAVES) ba_lin_kernel(BaArgs a, BaP
   if constexpr (PACK) {
     for (int k00 = k_begin; k00 < k_end; k00 += 2 * blockDim.x) {
       const int k0 = k00 + (int)threadIdx.x;
+      f2 xu = {0.0f, 0.0f}, yv = {0.0f, 0.0f};
+      if constexpr (MODE == BA_MODE_CALIB_RAW) pix_next(k0 + (int)blockDim.x < k_end, xu, yv);
       if (k0 < k_end) {
         const int k1 = k0 + (int)blockDim.x;
         const bool has1 = k1 < k_end;
@@ -576,8 +658,14 @@ __global__ void __launch_bounds__(256, BA_LIN_WAVES) ba_lin_kernel(BaArgs a, BaP
           if (has1) rec_n[k1] = n1;
         }
         f2 Xj[3];
+        if constexpr (MODE == BA_MODE_CALIB_RAW) {
+          Xj[2] = f2{Zj_base[(size_t)k0 * 3], Zj_base[(size_t)k1c * 3]};
+          Xj[0] = Xj[2] * xu;
+          Xj[1] = Xj[2] * yv;
+        } else {
 #pragma unroll
-        for (int c = 0; c < 3; c++) Xj[c] = f2{Xj_base[(size_t)k0 * 3 + c], Xj_base[(size_t)k1c * 3 + c]};
+          for (int c = 0; c < 3; c++) Xj[c] = f2{Xj_base[(size_t)k0 * 3 + c], Xj_base[(size_t)k1c * 3 + c]};
+        }
         rows(rec_expand<MODE>(R0), rec_expand<MODE>(R1), f2{n0, n1}, Xj, has1);
       }
       if (++run == BA_RUN_LEN) {
@@ -593,7 +681,7 @@ __global__ void __launch_bounds__(256, BA_LIN_WAVES) ba_lin_kernel(BaArgs a, BaP
     struct Round {
       float4 R0, R1;  // as stored (rec_load)
       f2 nI;          // rays: |Xi| of both points
-      f2 Xj[3];
+      f2 Xj[3];       // raw calib: {x_of_u[u], y_of_v[v], z_j}, multiplied out where the round is computed
     };
     auto fetch = [&](int k00, Round& r) {
       const int k0 = k00 + (int)threadIdx.x < k_end ? k00 + (int)threadIdx.x : k_begin;
@@ -601,8 +689,13 @@ __global__ void __launch_bounds__(256, BA_LIN_WAVES) ba_lin_kernel(BaArgs a, BaP
       r.R0 = rec_load<MODE>(rec, k0);
       r.R1 = rec_load<MODE>(rec, k1);
       if constexpr (MODE == BA_MODE_RAYS) r.nI = f2{rec_n[k0], rec_n[k1]};
+      if constexpr (MODE == BA_MODE_CALIB_RAW) {
+        r.Xj[2] = f2{Zj_base[(size_t)k0 * 3], Zj_base[(size_t)k1 * 3]};
+        pix_next(k00 + (int)threadIdx.x + (int)blockDim.x < k_end, r.Xj[0], r.Xj[1]);
+      } else {
 #pragma unroll
-      for (int c = 0; c < 3; c++) r.Xj[c] = f2{Xj_base[(size_t)k0 * 3 + c], Xj_base[(size_t)k1 * 3 + c]};
+        for (int c = 0; c < 3; c++) r.Xj[c] = f2{Xj_base[(size_t)k0 * 3 + c], Xj_base[(size_t)k1 * 3 + c]};
+      }
     };
     Round cur;
     fetch(k_begin, cur);
@@ -613,6 +706,10 @@ __global__ void __launch_bounds__(256, BA_LIN_WAVES) ba_lin_kernel(BaArgs a, BaP
       if (k0 < k_end) {
         f2 nI = {0.0f, 0.0f};
         if constexpr (MODE == BA_MODE_RAYS) nI = cur.nI;
+        if constexpr (MODE == BA_MODE_CALIB_RAW) {
+          cur.Xj[0] = cur.Xj[2] * cur.Xj[0];
+          cur.Xj[1] = cur.Xj[2] * cur.Xj[1];
+        }
         rows(rec_expand<MODE>(cur.R0), rec_expand<MODE>(cur.R1), nI, cur.Xj, k0 + (int)blockDim.x < k_end);
       }
       if (++run == BA_RUN_LEN) {
@@ -1425,6 +1522,8 @@ extern "C" hipError_t m3s_launch_ba_pack(const BaArgs* a, const BaParams* p, int
   const dim3 g((unsigned)blocks);
   if (p->mode == BA_MODE_CALIB)
     hipLaunchKernelGGL(m3s::ba_pack_kernel<BA_MODE_CALIB>, g, dim3(256), 0, s, *a, *p, n_pack, tiles);
+  else if (p->mode == BA_MODE_CALIB_RAW)
+    hipLaunchKernelGGL(m3s::ba_pack_kernel<BA_MODE_CALIB_RAW>, g, dim3(256), 0, s, *a, *p, n_pack, tiles);
   else if (p->mode == BA_MODE_RAYS)
     hipLaunchKernelGGL(m3s::ba_pack_kernel<BA_MODE_RAYS>, g, dim3(256), 0, s, *a, *p, n_pack, tiles);
   else
@@ -1436,19 +1535,23 @@ extern "C" hipError_t m3s_launch_ba_pack(const BaArgs* a, const BaParams* p, int
 extern "C" hipError_t m3s_launch_ba_lin(const BaArgs* a, const BaParams* p, int E_local, int pack, hipStream_t s) {
   if (E_local <= 0) return hipSuccess;
   const dim3 g(E_local * p->chunks);
-#define BA_LIN_LAUNCH(M)                                                                        \
+#define BA_LIN_LAUNCH(M, L)                                                                     \
   do {                                                                                          \
     if (pack)                                                                                   \
-      hipLaunchKernelGGL((m3s::ba_lin_kernel<M, true>), g, dim3(256), 0, s, *a, *p);              \
+      hipLaunchKernelGGL((m3s::ba_lin_kernel<M, true, L>), g, dim3(256), 0, s, *a, *p);           \
     else                                                                                        \
-      hipLaunchKernelGGL((m3s::ba_lin_kernel<M, false>), g, dim3(256), 0, s, *a, *p);             \
+      hipLaunchKernelGGL((m3s::ba_lin_kernel<M, false, L>), g, dim3(256), 0, s, *a, *p);          \
   } while (0)
   if (p->mode == BA_MODE_POINTS)
-    BA_LIN_LAUNCH(BA_MODE_POINTS);
+    BA_LIN_LAUNCH(BA_MODE_POINTS, false);
   else if (p->mode == BA_MODE_RAYS)
-    BA_LIN_LAUNCH(BA_MODE_RAYS);
+    BA_LIN_LAUNCH(BA_MODE_RAYS, false);
+  else if (p->mode == BA_MODE_CALIB_RAW && p->W + p->H <= BA_RAY_LDS)
+    BA_LIN_LAUNCH(BA_MODE_CALIB_RAW, true);
+  else if (p->mode == BA_MODE_CALIB_RAW)
+    BA_LIN_LAUNCH(BA_MODE_CALIB_RAW, false);
   else
-    BA_LIN_LAUNCH(BA_MODE_CALIB);
+    BA_LIN_LAUNCH(BA_MODE_CALIB, false);
 #undef BA_LIN_LAUNCH
   hipLaunchKernelGGL(m3s::ba_edge_kernel, dim3(E_local), dim3(64), 0, s, *a, *p, E_local);
   return hipGetLastError();

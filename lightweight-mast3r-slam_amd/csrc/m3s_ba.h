@@ -6,6 +6,7 @@
 #define BA_MODE_POINTS 0
 #define BA_MODE_RAYS 1
 #define BA_MODE_CALIB 2
+#define BA_MODE_CALIB_RAW 3  // calib residuals on points NOT constrained to their pixel rays (m3s.h M3S_BA_MODE_CALIB_RAW)
 
 #ifndef M3S_BA_SP_WAVES
 #define M3S_BA_SP_WAVES 16  // waves of the one-workgroup sparse factorisation (ba.hip) and of its cost model (abi.cpp)
@@ -87,6 +88,9 @@ struct BaArgs {
   int* bad;    // non-positive pivot seen by a multi-workgroup factor step (cleared by the assembly)
   int* stalled;  // sticky: a dataflow / LDS hand-off wait timed out in some solve of this plan (M3S_ESTALL)
   int force_stall;  // tests only (M3S_BA_FORCE_STALL): the dataflow waits are never satisfied
+  // raw calib (BA_MODE_CALIB_RAW): the plan's pixel-ray tables x_of_u (W floats) then y_of_v (H floats), the values of
+  // m3s_ba_calib_rays; null in every other mode
+  const float* ray_tab;
 };
 // bits of the factor kernel's failure word
 #define BA_BAD_LLT 1    // non-positive pivot: dx = 0 for this iteration (SimplicialLLT info != Success)

@@ -14,7 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # M3S_LIB: alternative build of the same library (kernel experiments); still the HIP library, no fallback
 LIB_PATH = os.environ.get("M3S_LIB") or os.path.join(os.path.dirname(_HERE), "lib", "libm3s.so")
 
-ABI_VERSION = 5  # include/m3s.h M3S_ABI_VERSION
+ABI_VERSION = 6  # include/m3s.h M3S_ABI_VERSION
 
 c_int, c_float, c_double, c_size_t, c_void_p = ctypes.c_int, ctypes.c_float, ctypes.c_double, ctypes.c_size_t, ctypes.c_void_p
 
@@ -102,6 +102,7 @@ _SIGS = {
     "m3s_ba_iterations": ([ctypes.POINTER(BaPlan), ctypes.POINTER(c_int), c_void_p], c_int),
     "m3s_ba_plan_info": ([ctypes.POINTER(BaPlan), ctypes.POINTER(c_int)], c_int),
     "m3s_ba_pattern_stats": ([c_void_p, c_void_p, c_int, c_int, ctypes.POINTER(c_int)], c_int),
+    "m3s_ba_calib_rays": ([ctypes.POINTER(BaConfig), c_void_p, c_void_p], c_int),
     "m3s_peak_fma_f32": ([c_void_p, c_int, c_int, c_void_p], c_int),
     "m3s_match_workspace_size": ([c_int] * 4, c_size_t),
     "m3s_match": ([c_void_p] * 7 + [c_int] * 5 + [c_float] * 3 + [c_int, c_int, c_void_p, c_size_t, c_void_p], c_int),
@@ -155,6 +156,18 @@ def ba_pattern_stats(ii, jj, Kp):
     out = (c_int * 6)()
     check(lib.m3s_ba_pattern_stats(c_void_p(ii.ctypes.data), c_void_p(jj.ctypes.data), len(ii), int(Kp), out))
     return tuple(out)
+
+
+def ba_calib_rays(cfg):
+    """Host-only: the pixel-ray tables (x_of_u (W), y_of_v (H), float32 arrays) a raw-calib BA plan (mode 3) builds
+    for the BaConfig ``cfg``: (u - cx) / fx and (v - cy) / fy in ``geometry.backproject``'s fp32 operation order."""
+    import numpy as np
+
+    lib = load(require_gpu=False)
+    x = np.empty(int(cfg.width), dtype=np.float32)
+    y = np.empty(int(cfg.height), dtype=np.float32)
+    check(lib.m3s_ba_calib_rays(ctypes.byref(cfg), c_void_p(x.ctypes.data), c_void_p(y.ctypes.data)))
+    return x, y
 
 
 def check(rc):

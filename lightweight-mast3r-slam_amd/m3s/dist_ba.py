@@ -23,7 +23,9 @@ import torch.distributed as dist
 
 from m3s import _lib
 
-BA_MODES = {"points": 0, "rays": 1, "calib": 2}
+# calib_raw (M3S_BA_MODE_CALIB_RAW): calib residuals on points NOT constrained to their pixel rays; the kernels apply
+# constrain_points_to_ray themselves (bit-identical to "calib" on the constrained points)
+BA_MODES = {"points": 0, "rays": 1, "calib": 2, "calib_raw": 3}
 M3S_ESTALL = -4  # include/m3s.h
 
 
@@ -221,7 +223,11 @@ def gauss_newton_sharded(mode, Twc, Xs, Cs, ii, jj, idx, valid, Q, cfg, max_iter
     full problem, replicated), Twc updated in place identically on every rank; returns [dx]. With
     ``Xs=None`` the keyframe points come zero-copy from ``keyframes`` (see ``HipShard``); with ``reuse`` and
     ``cache`` the records of unchanged edges carry over from the previous solve (``info``, a dict, receives
-    ``packed_edges`` / ``changed_keyframes``)."""
+    ``packed_edges`` / ``changed_keyframes``). The keyframes' own buffers are raw pointmaps: mode "calib" with
+    ``Xs=None`` therefore runs "calib_raw", which constrains them to their pixel rays in the kernels (the stacked
+    "calib" call expects ``constrain_points_to_ray(Xs)``, as the reference's operator)."""
+    if mode == "calib" and Xs is None:
+        mode = "calib_raw"
     rank = dist.get_rank(group) if dist.is_available() and dist.is_initialized() else 0
     world = dist.get_world_size(group) if dist.is_available() and dist.is_initialized() else 1
     e0, e1 = shard_range(ii.shape[0], rank, world)

@@ -1,12 +1,15 @@
 """``FactorGraph`` with the reference surface (``/root/reference/mast3r_slam/global_opt.py:14-226``).
 
 Edge insertion (``add_factors``) batches the symmetric matches of all new edges through the fused
-HIP matcher; ``solve_GN_rays`` / ``solve_GN_calib`` run the split BA API of ``m3s.dist_ba`` with record reuse
+HIP matcher; ``solve_GN_rays`` / ``solve_GN_calib`` run the split BA API of ``m3s.dist_ba`` on the keyframes' own
+buffers (no stacked copy; calib constrains the points to their pixel rays in the kernels) with record reuse
 across solves (only new edges and edges of changed keyframes are re-packed; bit-identical to a fresh solve) and,
 when ``torch.distributed`` is initialised with more than one rank, edge-sharded over RCCL (identical result on
 every rank). With ``reuse_records = False`` a single-GPU solve calls the drop-in ``mast3r_slam_backends``
 operators.
 """
+import os
+
 import numpy as np
 import torch
 import torch.distributed as dist
@@ -154,6 +157,16 @@ class FactorGraph:
         self.ba_info = {}
         return {"reuse": (edge_uid, kf_uid), "cache": self._records, "info": self.ba_info}
 
+    def _calib_zero_copy(self, K):
+        """Whether solve_GN_calib may read the keyframes in place. The raw-calib plan builds its ray tables as torch
+        does with K on the keyframes' device ((u - cx) / fx, a true fp32 division); with K elsewhere (a CPU tensor
+        against device points) torch multiplies by the reciprocal instead, which rounds differently, so that case keeps
+        the stacked path and its exact values."""
+        if os.environ.get("M3S_BA_CALIB_ZERO_COPY", "1") == "0":
+            return False
+        X0 = self.frames[0].X_canon
+        return torch.is_tensor(K) and K.dtype == torch.float32 and torch.is_tensor(X0) and K.device == X0.device
+
     def solve_GN_rays(self):
         """global_opt.py:123-161, with the keyframe points read in place (no torch.stack of K x N x 16 B)."""
         cfg = self.cfg
@@ -187,20 +200,33 @@ class FactorGraph:
         self.frames.update_T_WCs(T_WCs[pin:], unique_kf_idx[pin:])
 
     def solve_GN_calib(self):
-        """global_opt.py:163-226."""
+        """global_opt.py:163-226, with the keyframe points read in place: the raw-calib BA mode constrains them to
+        their pixel rays in the kernels (bit-identical to constrain_points_to_ray on the stacked copy), so neither the
+        torch.stack of K x N x 12 B, nor the pixel grid, nor the constrained copy is made. M3S_BA_CALIB_ZERO_COPY=0
+        keeps the stacked path."""
         cfg = self.cfg
         K = self.K
         pin = self._pin(cfg)
         unique_kf_idx = self.get_unique_kf_idx()
         if unique_kf_idx.numel() <= max(pin, 1):
             return
-        Xs, T_WCs, Cs = self.get_poses_points(unique_kf_idx)
         img_size = frame_img_size(self.frames[0])
-        Xs = constrain_points_to_ray(img_size, Xs, K)
-        ii, jj, idx_ii2jj, valid_match, Q_ii2jj = self.prep_two_way_edges()
-        pose_data = T_WCs.data[:, 0, :]
         height, width = img_size
+        ii, jj, idx_ii2jj, valid_match, Q_ii2jj = self.prep_two_way_edges()
         rk = self._reuse_kw(unique_kf_idx)
+        zc = self.get_poses_keyframes(unique_kf_idx) if self._calib_zero_copy(K) else None
+        if zc is not None:
+            from m3s.dist_ba import gauss_newton_sharded
+
+            T_WCs, keyframes = zc
+            gauss_newton_sharded("calib", T_WCs.data[:, 0, :], None, None, ii, jj, idx_ii2jj, valid_match, Q_ii2jj,
+                                 cfg, cfg["max_iters"], cfg["delta_norm"], K=K, height=height, width=width,
+                                 group=self.group, keyframes=keyframes, **rk)
+            self.frames.update_T_WCs(T_WCs[pin:], unique_kf_idx[pin:])
+            return
+        Xs, T_WCs, Cs = self.get_poses_points(unique_kf_idx)
+        Xs = constrain_points_to_ray(img_size, Xs, K)
+        pose_data = T_WCs.data[:, 0, :]
         if self._sharded() or rk:
             from m3s.dist_ba import gauss_newton_sharded
 
