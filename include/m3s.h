@@ -22,7 +22,7 @@
 extern "C" {
 #endif
 
-#define M3S_ABI_VERSION 6
+#define M3S_ABI_VERSION 7
 
 #define M3S_OK 0
 #define M3S_EINVAL -1  /* bad shape / argument (reference: TORCH_CHECK -> RuntimeError) */
@@ -38,8 +38,8 @@ const char* m3s_last_error(void);
 /* Per-kernel HIP-event timing (no reference counterpart; the reference's profiler.py wraps regions
  * with torch.cuda.synchronize). When enabled, every launch group is bracketed by hipEvents on its
  * own stream under a name: prep_rays, proj_occlusion, refine_lin, track_setup, gn_iters,
- * ba_linearize, ba_solve. query synchronises the recorded events. (m3s_match runs the projection
- * search inside the refine launch where the tile path is taken: refine_lin then covers both and
+ * ba_linearize, ba_solve, map_count, map_write. query synchronises the recorded events. (m3s_match runs the
+ * projection search inside the refine launch where the tile path is taken: refine_lin then covers both and
  * proj_occlusion has no spans, count 0; M3S_MATCH_FUSE_PROJ=0 separates them.) */
 void m3s_timing_enable(int on);
 void m3s_timing_reset(void);
@@ -287,6 +287,44 @@ int m3s_codebook_prepare(const float* centroids, int C, int D, void* codebook, s
 size_t m3s_quantize_workspace_size(int C, int D, int M, int k);
 int m3s_quantize(const void* codebook, int C, int D, const float* qvecs, int M, int k, int64_t* topk_out,
                  void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- map export: the confidence-filtered world point cloud of the keyframes ----
+ * Replaces the per-keyframe host loop of evaluate.save_reconstruction (mast3r_slam/evaluate.py:47-70, called at
+ * main.py:370-376; the viewer's live cloud, visualization.py:38,351, is the same filter): constrain_points_to_ray
+ * (geometry.py:37-42) in calib mode, T_WC.act, get_average_conf() > c_conf_threshold, boolean indexing of points and
+ * colours, np.concatenate. Rows come in the reference's order: keyframes in table order, pixels ascending.
+ * Pixel n of keyframe k is kept iff C_k[n] * float32(1 / N_avg[k]) > c_conf_threshold (strict: NaN drops; the
+ * keyframe table and its average are those of m3s_ba_keyframes). Its point is X_k[n], or with calib = 1 the point
+ * (z x_of_u[u], z y_of_v[v], z) of its depth z = X_k[n].z on the ray of pixel u = n % width, v = n / width (the
+ * tables of m3s_ba_calib_rays; bit-identical to constrain_points_to_ray; checks: N == height * width, both below
+ * 65536), mapped to the world by Twc[k] in Sim3.act's fp32 operation order, one rounding per operation.
+ * layout M3S_MAP_SOA: out (M,3) f32 and out_rgb (M,3) u8; M3S_MAP_PLY: out (M,15) bytes, the vertex records
+ * (x, y, z little-endian f32, then r, g, b) of a binary little-endian PLY body (evaluate.save_ply, :88-106). */
+#define M3S_MAP_SOA 0
+#define M3S_MAP_PLY 1
+typedef struct m3s_map_config {
+  int calib;
+  float fx, fy, cx, cy; /* calib: K[0,0], K[1,1], K[0,2], K[1,2] (host values) */
+  int height, width;
+  float c_conf_threshold;
+  int layout;
+} m3s_map_config;
+size_t m3s_map_workspace_size(int Kp, int N);
+/* Pass A + scan (evaluate.py:61-64, the mask): reads only C, stores 1 validity bit per point, the first output row of
+ * every block of pixels and the counts in the workspace, whose header then records Kp, N, the threshold and the
+ * total. Synchronises the stream. counts_out (host, Kp entries, nullable): rows per keyframe; total_out (host): M. */
+int m3s_map_count(const m3s_map_config* cfg, const m3s_ba_keyframes* kf, int Kp, int N, int64_t* counts_out,
+                  int64_t* total_out, void* workspace, size_t workspace_bytes, void* stream);
+/* Pass B (evaluate.py:54-60, 65-68): transform and compact the points that were valid AT THE COUNT (the stored bits;
+ * C is not read again, so a keyframe that tracking fuses into between the two calls cannot move a row). Twc (Kp,8)
+ * device. rgb: host array of Kp device pointers to (N,3) u8 colours, or NULL (geometry only: SOA out_rgb must then be
+ * NULL, PLY colour bytes are 0). Rows at or beyond `capacity` are never written. The launch is asynchronous on
+ * `stream`; before it the workspace header is read back (a 32-byte copy that waits for the stream's earlier work).
+ * M3S_EINVAL: no count preceded the write on this workspace, Kp / N / threshold differ from that count's, capacity
+ * below its total, a null table entry, a bad layout, a failed calib shape check; M3S_ESPACE: short workspace. */
+int m3s_map_write(const m3s_map_config* cfg, const m3s_ba_keyframes* kf, const float* Twc, const uint8_t* const* rgb,
+                  int Kp, int N, void* out, uint8_t* out_rgb, int64_t capacity, void* workspace, size_t workspace_bytes,
+                  void* stream);
 
 /* Measured-peak probe (no reference counterpart; bench.py's roofline context):
  * blocks x 256 lanes x iters x 8 chains of v_fma_f32 (2 flops each) on `stream`. */

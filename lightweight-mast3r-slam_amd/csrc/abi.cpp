@@ -19,6 +19,7 @@
 #include "m3s_ba.h"
 #include "ba_pattern.h"
 #include "m3s_track.h"
+#include "m3s_map.h"
 
 extern "C" {
 hipError_t m3s_launch_prep(const float*, float*, const float*, void*, int, int, int, int, int, float*, hipStream_t);
@@ -49,6 +50,8 @@ hipError_t m3s_launch_ba_kf_compare(const BaKfCopy*, int, int, uint8_t*, hipStre
 hipError_t m3s_launch_ba_solve(const BaArgs*, int, int, float, const int*, const int*, const int*, hipStream_t);
 hipError_t m3s_launch_ba_solve_dense(const BaArgs*, int, int, float, hipStream_t);
 hipError_t m3s_launch_peak_fma_f32(float*, int, int, hipStream_t);
+hipError_t m3s_launch_map_count(const MapArgs*, hipStream_t);
+hipError_t m3s_launch_map_write(const MapArgs*, hipStream_t);
 hipError_t m3s_launch_rq_prep(const float*, int, int, int, int, int, uint4*, int, float, float*, hipStream_t);
 hipError_t m3s_launch_rq_topk(const uint4*, const float*, const uint4*, const float*, int, int, int, int, int,
                               unsigned long long*, int64_t*, hipStream_t);
@@ -594,6 +597,10 @@ void ba_calib_rays(const m3s_ba_config* cfg, float* x_of_u, float* y_of_v) {
   }
 }
 
+// The factor that turns a keyframe's confidence sum into its average: torch's C / N on a device tensor is
+// C * float32(1/N) (Frame.get_average_conf, frame.py:93-94). One definition for the BA pack and the map export.
+inline float conf_scale(float n_avg) { return 1.0f / n_avg; }
+
 constexpr int BA_DENSE_MAX_POSES = 1025;  // dense fallback workspace: (2n+1) n doubles, ~0.8 GB at this size
 
 // factor blocks of the densest possible pattern (every pose coupled to every other)
@@ -665,6 +672,22 @@ PlanStage& plan_stage() {
   (void)hipGetDevice(&dev);
   std::lock_guard<std::mutex> lock(map_mu);
   return stages[dev];  // std::map nodes never move
+}
+// With st.mu held: wait until the previous upload through the stage has landed and make it hold `bytes`.
+hipError_t stage_reserve(PlanStage& st, size_t bytes) {
+  hipError_t e = hipSuccess;
+  if (st.pending) e = hipEventSynchronize(st.landed);
+  st.pending = false;
+  if (e == hipSuccess && !st.landed) e = hipEventCreateWithFlags(&st.landed, hipEventDisableTiming);
+  if (e == hipSuccess && st.cap < bytes) {
+    if (st.buf) (void)hipHostFree(st.buf);
+    st.buf = nullptr;
+    st.cap = 0;
+    const size_t want = std::max(bytes, (size_t)1 << 20);
+    e = hipHostMalloc((void**)&st.buf, want, hipHostMallocDefault);
+    if (e == hipSuccess) st.cap = want;
+  }
+  return e;
 }
 
 // Record reuse across plans on one workspace (m3s_ba_make_plan_reuse). The backend solves once per new keyframe
@@ -922,18 +945,7 @@ PlanSym* plan_symbolic(const BaPlanImpl* P, hipStream_t s, bool upload, int* rc)
     if (!Y->image.empty()) {
       PlanStage& st = plan_stage();
       std::lock_guard<std::mutex> sl(st.mu);
-      hipError_t e = hipSuccess;
-      if (st.pending) e = hipEventSynchronize(st.landed);
-      st.pending = false;
-      if (e == hipSuccess && !st.landed) e = hipEventCreateWithFlags(&st.landed, hipEventDisableTiming);
-      if (e == hipSuccess && st.cap < Y->image.size()) {
-        if (st.buf) (void)hipHostFree(st.buf);
-        st.buf = nullptr;
-        st.cap = 0;
-        const size_t want = std::max(Y->image.size(), (size_t)1 << 20);
-        e = hipHostMalloc((void**)&st.buf, want, hipHostMallocDefault);
-        if (e == hipSuccess) st.cap = want;
-      }
+      hipError_t e = stage_reserve(st, Y->image.size());
       if (e == hipSuccess) {
         memcpy(st.buf, Y->image.data(), Y->image.size());
         e = hipMemcpyAsync(Y->dst, st.buf, Y->image.size(), hipMemcpyHostToDevice, s);
@@ -1218,17 +1230,7 @@ int ba_make_plan_impl(const m3s_ba_config* cfg, float* Twc, const float* const* 
   {
     PlanStage& st = plan_stage();
     std::lock_guard<std::mutex> lock(st.mu);
-    if (st.pending) HIP_TRY(hipEventSynchronize(st.landed), "ba stage wait");
-    st.pending = false;
-    if (!st.landed) HIP_TRY(hipEventCreateWithFlags(&st.landed, hipEventDisableTiming), "ba stage event");
-    if (st.cap < total) {
-      if (st.buf) (void)hipHostFree(st.buf);
-      st.buf = nullptr;
-      st.cap = 0;
-      const size_t want = std::max(total, (size_t)1 << 20);
-      HIP_TRY(hipHostMalloc((void**)&st.buf, want, hipHostMallocDefault), "ba stage alloc");
-      st.cap = want;
-    }
+    HIP_TRY(stage_reserve(st, total), "ba stage");
     size_t off = 0;
     for (const Sec& x : secs) {
       if (x.bytes) memcpy(st.buf + off, x.src, x.bytes);
@@ -1335,7 +1337,7 @@ extern "C" int m3s_ba_make_plan_kf_reuse(const m3s_ba_config* cfg, float* Twc, c
   for (int k = 0; k < Kp; k++) {
     M3S_CHECK(kf->X[k] && kf->C[k], "ba: null keyframe buffer");
     M3S_CHECK(kf->N_avg[k] > 0.0f, "ba: keyframe fusion count N must be positive");
-    sh[k] = 1.0f / kf->N_avg[k];  // torch's C / N on a device tensor: C * float32(1/N)
+    sh[k] = conf_scale(kf->N_avg[k]);
   }
   return ba_make_plan_impl(cfg, Twc, kf->X, kf->C, sh.data(), Kp, N, ii, jj, E, e0, e1, idx, valid, Q, delta_thresh,
                            dx_out, reuse ? reuse->edge_uid : nullptr, reuse ? reuse->kf_uid : nullptr, workspace,
@@ -1585,6 +1587,205 @@ extern "C" int m3s_quantize(const void* codebook, int C, int D, const float* qve
     Span sp("quantize_topk", s);
     HIP_TRY(m3s_launch_rq_topk(cfrag, cn, qfrag, qn, S, rq_rows_padded(C) / RQ_ROWS, G, M, k, cand, topk_out, s),
             "quantize topk launch");
+  }
+  return M3S_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// map export (evaluate.py:47-70; kernels in map.hip)
+// ------------------------------------------------------------------------------------------
+namespace {
+constexpr int MAP_MAX_BLOCKS = 1 << 23;  // one block per MAP_TILE pixels: the grid of both passes
+
+struct MapWs {
+  MapHeader* header;
+  uint64_t* mask;
+  uint32_t* bcnt;
+  int64_t* boff;
+  int64_t* kcnt;
+  char* tab_count;  // C pointers, scales (uploaded by the count)
+  char* tab_write;  // X pointers, rgb pointers, ray tables (uploaded by the write)
+};
+
+inline int map_bpk(int N) { return (N + MAP_TILE - 1) / MAP_TILE; }
+inline size_t map_tab_count_bytes(int Kp) { return (size_t)Kp * 8 + 16 + (size_t)Kp * 4 + 16; }
+inline size_t map_tab_write_bytes(int Kp, int N) {
+  return 2 * ((size_t)Kp * 8 + 16) + ba_ray_tab_floats(N) * 4 + 16;
+}
+
+size_t map_carve(Carver& c, int Kp, int N, MapWs* w) {
+  const size_t E = (size_t)Kp * map_bpk(N);
+  w->header = c.take<MapHeader>(1);
+  w->mask = c.take<uint64_t>(E * MAP_WORDS);
+  w->bcnt = c.take<uint32_t>(E);
+  w->boff = c.take<int64_t>(E + 1);
+  w->kcnt = c.take<int64_t>((size_t)Kp + 1);
+  w->tab_count = c.take<char>(map_tab_count_bytes(Kp));
+  w->tab_write = c.take<char>(map_tab_write_bytes(Kp, N));
+  return c.off;
+}
+
+bool map_sizes_ok(int Kp, int N) {
+  return Kp >= 1 && Kp <= M3S_BA_MAX_POSES && N >= 1 && N <= (1 << 28) && (int64_t)Kp * map_bpk(N) <= MAP_MAX_BLOCKS;
+}
+
+// the argument checks both entry points share; no device is touched
+int map_check(const m3s_map_config* cfg, const m3s_ba_keyframes* kf, int Kp, int N, const void* ws, size_t ws_bytes) {
+  M3S_CHECK(cfg, "map: null config");
+  M3S_CHECK(cfg->layout == M3S_MAP_SOA || cfg->layout == M3S_MAP_PLY, "map: layout must be M3S_MAP_SOA or M3S_MAP_PLY");
+  M3S_CHECK(cfg->calib == 0 || cfg->calib == 1, "map: calib must be 0 or 1");
+  M3S_CHECK(map_sizes_ok(Kp, N), "map: bad Kp or N");
+  if (cfg->calib) {
+    M3S_CHECK(cfg->height > 0 && cfg->width > 0 && cfg->height < 65536 && cfg->width < 65536,
+              "map: calib needs 0 < height, width < 65536");
+    M3S_CHECK((int64_t)cfg->height * cfg->width == N, "map: calib needs N == height * width");
+  }
+  M3S_CHECK(kf && kf->X && kf->C && kf->N_avg, "map: null keyframe table");
+  M3S_CHECK(ws, "map: null workspace");
+  if (ws_bytes < m3s_map_workspace_size(Kp, N)) return fail(M3S_ESPACE, "map: workspace too small");
+  return M3S_OK;
+}
+
+// host tables -> device through the per-device pinned stage (one copy; the stage is reused once it has landed)
+struct MapSec {
+  const void* src;
+  size_t bytes;
+  const void** dst;
+};
+int map_upload(char* dev, const MapSec* secs, int nsec, hipStream_t s) {
+  size_t total = 0;
+  for (int i = 0; i < nsec; i++) total += (secs[i].bytes + 15) & ~(size_t)15;
+  PlanStage& st = plan_stage();
+  std::lock_guard<std::mutex> lock(st.mu);
+  HIP_TRY(stage_reserve(st, total), "map stage");
+  size_t off = 0;
+  for (int i = 0; i < nsec; i++) {
+    if (secs[i].bytes) memcpy(st.buf + off, secs[i].src, secs[i].bytes);
+    *secs[i].dst = dev + off;
+    off += (secs[i].bytes + 15) & ~(size_t)15;
+  }
+  HIP_TRY(hipMemcpyAsync(dev, st.buf, total, hipMemcpyHostToDevice, s), "map upload");
+  HIP_TRY(hipEventRecord(st.landed, s), "map stage record");
+  st.pending = true;
+  return M3S_OK;
+}
+}  // namespace
+
+extern "C" size_t m3s_map_workspace_size(int Kp, int N) {
+  if (!map_sizes_ok(Kp, N)) return 0;
+  Carver c(nullptr);
+  MapWs w;
+  return map_carve(c, Kp, N, &w);
+}
+
+extern "C" int m3s_map_count(const m3s_map_config* cfg, const m3s_ba_keyframes* kf, int Kp, int N, int64_t* counts_out,
+                             int64_t* total_out, void* ws, size_t ws_bytes, void* stream) {
+  const int rc = map_check(cfg, kf, Kp, N, ws, ws_bytes);
+  if (rc != M3S_OK) return rc;
+  M3S_CHECK(total_out, "map: null total_out");
+  std::vector<float> sh(Kp);
+  for (int k = 0; k < Kp; k++) {
+    M3S_CHECK(kf->C[k], "map: null keyframe buffer");
+    M3S_CHECK(kf->N_avg[k] > 0.0f, "map: keyframe fusion count N must be positive");
+    sh[k] = conf_scale(kf->N_avg[k]);
+  }
+  Carver c(ws);
+  MapWs w;
+  map_carve(c, Kp, N, &w);
+  hipStream_t s = (hipStream_t)stream;
+  MapArgs a{};
+  a.Kp = Kp;
+  a.N = N;
+  a.bpk = map_bpk(N);
+  a.thresh = cfg->c_conf_threshold;
+  a.header = w.header;
+  a.mask = w.mask;
+  a.bcnt = w.bcnt;
+  a.boff = w.boff;
+  a.kcnt = w.kcnt;
+  // a count that fails half way leaves no header a write would accept
+  HIP_TRY(hipMemsetAsync(w.header, 0, sizeof(MapHeader), s), "map header reset");
+  const MapSec secs[] = {
+      {kf->C, sizeof(const float*) * Kp, (const void**)&a.C},
+      {sh.data(), sizeof(float) * Kp, (const void**)&a.scale},
+  };
+  const int up = map_upload(w.tab_count, secs, 2, s);
+  if (up != M3S_OK) return up;
+  {
+    Span sp("map_count", s);
+    HIP_TRY(m3s_launch_map_count(&a, s), "map count launch");
+  }
+  std::vector<int64_t> kc((size_t)Kp + 1);
+  HIP_TRY(hipMemcpyAsync(kc.data(), w.kcnt, sizeof(int64_t) * kc.size(), hipMemcpyDeviceToHost, s), "map counts copy");
+  HIP_TRY(hipStreamSynchronize(s), "map count sync");
+  if (counts_out) memcpy(counts_out, kc.data(), sizeof(int64_t) * Kp);
+  *total_out = kc[Kp];
+  return M3S_OK;
+}
+
+extern "C" int m3s_map_write(const m3s_map_config* cfg, const m3s_ba_keyframes* kf, const float* Twc,
+                             const uint8_t* const* rgb, int Kp, int N, void* out, uint8_t* out_rgb, int64_t capacity,
+                             void* ws, size_t ws_bytes, void* stream) {
+  const int rc = map_check(cfg, kf, Kp, N, ws, ws_bytes);
+  if (rc != M3S_OK) return rc;
+  M3S_CHECK(Twc, "map: null poses");
+  M3S_CHECK(capacity >= 0 && (out || capacity == 0), "map: null output");
+  M3S_CHECK(((uintptr_t)out & 3) == 0 && ((uintptr_t)out_rgb & 3) == 0, "map: outputs must be 4-byte aligned");
+  if (cfg->layout == M3S_MAP_SOA)
+    M3S_CHECK((rgb != nullptr) == (out_rgb != nullptr), "map: SOA colours need both rgb and out_rgb, or neither");
+  else
+    M3S_CHECK(out_rgb == nullptr, "map: the PLY layout has no separate colour output");
+  for (int k = 0; k < Kp; k++) M3S_CHECK(kf->X[k] && (!rgb || rgb[k]), "map: null keyframe buffer");
+  Carver c(ws);
+  MapWs w;
+  map_carve(c, Kp, N, &w);
+  hipStream_t s = (hipStream_t)stream;
+  // the count this write belongs to: its header, read back (32 B; orders after the stream's earlier work)
+  MapHeader h;
+  HIP_TRY(hipMemcpyAsync(&h, w.header, sizeof(h), hipMemcpyDeviceToHost, s), "map header copy");
+  HIP_TRY(hipStreamSynchronize(s), "map header sync");
+  M3S_CHECK(h.magic == MAP_MAGIC, "map: no m3s_map_count preceded this write on the workspace");
+  uint32_t tb;
+  memcpy(&tb, &cfg->c_conf_threshold, 4);
+  M3S_CHECK(h.Kp == Kp && h.N == N && h.thresh_bits == tb, "map: shapes or threshold differ from the workspace's count");
+  M3S_CHECK(capacity >= h.total, "map: capacity below the counted total");
+  if (h.total == 0) return M3S_OK;
+  MapArgs a{};
+  a.Kp = Kp;
+  a.N = N;
+  a.bpk = map_bpk(N);
+  a.thresh = cfg->c_conf_threshold;
+  a.calib = cfg->calib;
+  a.W = cfg->calib ? cfg->width : 0;
+  a.layout = cfg->layout;
+  a.capacity = capacity;
+  a.header = w.header;
+  a.mask = w.mask;
+  a.bcnt = w.bcnt;
+  a.boff = w.boff;
+  a.kcnt = w.kcnt;
+  a.Twc = Twc;
+  a.out = out;
+  a.out_rgb = out_rgb;
+  std::vector<float> ray_tab;
+  if (cfg->calib) {
+    m3s_ba_config bc{};
+    bc.fx = cfg->fx, bc.fy = cfg->fy, bc.cx = cfg->cx, bc.cy = cfg->cy;
+    bc.height = cfg->height, bc.width = cfg->width;
+    ray_tab.resize((size_t)cfg->width + cfg->height);
+    ba_calib_rays(&bc, ray_tab.data(), ray_tab.data() + cfg->width);
+  }
+  const MapSec secs[] = {
+      {kf->X, sizeof(const float*) * Kp, (const void**)&a.X},
+      {rgb, rgb ? sizeof(const uint8_t*) * Kp : 0, (const void**)&a.rgb},
+      {ray_tab.data(), sizeof(float) * ray_tab.size(), (const void**)&a.ray_tab},
+  };
+  const int up = map_upload(w.tab_write, secs, 3, s);
+  if (up != M3S_OK) return up;
+  if (!rgb) a.rgb = nullptr;
+  {
+    Span sp("map_write", s);
+    HIP_TRY(m3s_launch_map_write(&a, s), "map write launch");
   }
   return M3S_OK;
 }

@@ -1,7 +1,8 @@
 """m3s — MI355X-native MASt3R-SLAM tracking hot path (host side over libm3s.so).
 
 Modules: matching (fused dense matcher), tracker (FrameTracker), global_opt (FactorGraph),
-dist_ba (edge-sharded multi-GPU BA), sim3 (lietorch-compatible Sim3), frame, config, synthetic.
+dist_ba (edge-sharded multi-GPU BA), evaluate (map and trajectory export), sim3 (lietorch-compatible Sim3),
+frame, config, synthetic.
 The drop-in operator module is the sibling package ``mast3r_slam_backends``.
 """
 import os

@@ -14,7 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # M3S_LIB: alternative build of the same library (kernel experiments); still the HIP library, no fallback
 LIB_PATH = os.environ.get("M3S_LIB") or os.path.join(os.path.dirname(_HERE), "lib", "libm3s.so")
 
-ABI_VERSION = 6  # include/m3s.h M3S_ABI_VERSION
+ABI_VERSION = 7  # include/m3s.h M3S_ABI_VERSION
 
 c_int, c_float, c_double, c_size_t, c_void_p = ctypes.c_int, ctypes.c_float, ctypes.c_double, ctypes.c_size_t, ctypes.c_void_p
 
@@ -27,6 +27,15 @@ class BaConfig(ctypes.Structure):
 
 class BaKeyframes(ctypes.Structure):
     _fields_ = [("X", ctypes.POINTER(c_void_p)), ("C", ctypes.POINTER(c_void_p)), ("N_avg", ctypes.POINTER(c_float))]
+
+
+class MapConfig(ctypes.Structure):
+    _fields_ = [("calib", c_int), ("fx", c_float), ("fy", c_float), ("cx", c_float), ("cy", c_float),
+                ("height", c_int), ("width", c_int), ("c_conf_threshold", c_float), ("layout", c_int)]
+
+
+MAP_SOA, MAP_PLY = 0, 1
+EINVAL, EHIP, ESPACE = -1, -2, -3
 
 
 class BaReuse(ctypes.Structure):
@@ -103,6 +112,12 @@ _SIGS = {
     "m3s_ba_plan_info": ([ctypes.POINTER(BaPlan), ctypes.POINTER(c_int)], c_int),
     "m3s_ba_pattern_stats": ([c_void_p, c_void_p, c_int, c_int, ctypes.POINTER(c_int)], c_int),
     "m3s_ba_calib_rays": ([ctypes.POINTER(BaConfig), c_void_p, c_void_p], c_int),
+    "m3s_map_workspace_size": ([c_int, c_int], c_size_t),
+    "m3s_map_count": ([ctypes.POINTER(MapConfig), ctypes.POINTER(BaKeyframes), c_int, c_int,
+                       ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64), c_void_p, c_size_t, c_void_p],
+                      c_int),
+    "m3s_map_write": ([ctypes.POINTER(MapConfig), ctypes.POINTER(BaKeyframes), c_void_p, ctypes.POINTER(c_void_p),
+                       c_int, c_int, c_void_p, c_void_p, ctypes.c_int64, c_void_p, c_size_t, c_void_p], c_int),
     "m3s_peak_fma_f32": ([c_void_p, c_int, c_int, c_void_p], c_int),
     "m3s_match_workspace_size": ([c_int] * 4, c_size_t),
     "m3s_match": ([c_void_p] * 7 + [c_int] * 5 + [c_float] * 3 + [c_int, c_int, c_void_p, c_size_t, c_void_p], c_int),
