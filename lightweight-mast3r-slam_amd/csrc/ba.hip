@@ -869,7 +869,6 @@ __device__ __forceinline__ void ba_assemble_one(const BaArgs& a, int nL, int b, 
 
 constexpr int SP_WAVES = 16;                 // waves of the factor workgroup
 static_assert(SP_WAVES == M3S_BA_SP_WAVES, "the host's schedules assume the kernel's wave count");
-constexpr int SP_PLAN_BYTES = 144 * 1024;   // LDS for the plan's loop tables and the solution x
 
 // 1/sqrt(d) for d > 0: the v_rsq_f64 estimate (~2^-22 relative) refined by ONE Newton step (~2^-44)
 __device__ __forceinline__ double rsqrt_nr(double d) {

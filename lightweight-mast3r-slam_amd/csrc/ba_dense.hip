@@ -3,7 +3,7 @@
 // The block-sparse factorisation (ba.hip, ba_sparse_factor_kernel) runs down the elimination tree inside
 // one workgroup; on graphs whose fill makes the factor nearly dense (e.g. loop closures to random earlier
 // keyframes) its level count and update volume approach the dense case, and this multi-CU dense
-// factorisation is faster. The plan picks one of the two from the symbolic factorisation (abi.cpp).
+// factorisation is faster. The plan picks one of the two from the symbolic factorisation (abi_ba.cpp).
 // Same system, same order (the plan's minimum-degree permutation), fp64, deterministic (every element
 // has one owner and a fixed summation order), so ranks stay bit-identical either way.
 //

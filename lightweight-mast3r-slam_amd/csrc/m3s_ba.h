@@ -1,4 +1,5 @@
-// Internal (non-ABI) structs shared by ba.hip and abi.cpp. The public C ABI is include/m3s.h.
+// Internal (non-ABI) structs, constants and launchers shared by ba.hip, ba_dense.hip and abi_ba.cpp. The public C ABI
+// is include/m3s.h.
 #pragma once
 #include <stdint.h>
 #include <hip/hip_runtime.h>
@@ -9,8 +10,11 @@
 #define BA_MODE_CALIB_RAW 3  // calib residuals on points NOT constrained to their pixel rays (m3s.h M3S_BA_MODE_CALIB_RAW)
 
 #ifndef M3S_BA_SP_WAVES
-#define M3S_BA_SP_WAVES 16  // waves of the one-workgroup sparse factorisation (ba.hip) and of its cost model (abi.cpp)
+#define M3S_BA_SP_WAVES 16  // waves of the one-workgroup sparse factorisation (ba.hip) and of its cost model (abi_ba.cpp)
 #endif
+namespace m3s {
+constexpr int SP_PLAN_BYTES = 144 * 1024;  // LDS of the one-workgroup factor kernel: the plan's loop tables and x
+}
 
 struct BaParams {
   int mode;
@@ -95,3 +99,12 @@ struct BaArgs {
 // bits of the factor kernel's failure word
 #define BA_BAD_LLT 1    // non-positive pivot: dx = 0 for this iteration (SimplicialLLT info != Success)
 #define BA_BAD_STALL 2  // a bounded dataflow wait timed out
+
+extern "C" {
+hipError_t m3s_launch_ba_kf_compare(const BaKfCopy* kf, int Kp, int N, uint8_t* dirty, hipStream_t s);
+hipError_t m3s_launch_ba_pack(const BaArgs* a, const BaParams* p, int n_pack, hipStream_t s);
+hipError_t m3s_launch_ba_lin(const BaArgs* a, const BaParams* p, int E_local, int pack, hipStream_t s);
+hipError_t m3s_launch_ba_solve(const BaArgs* a, int K, int nL, float delta_thresh, const int* step_tasks,
+                               const int* step_base, const int* step_na, hipStream_t s);
+hipError_t m3s_launch_ba_solve_dense(const BaArgs* a, int K, int nL, float delta_thresh, hipStream_t s);  // ba_dense.hip
+}

@@ -1,4 +1,4 @@
-// Internal (non-ABI) structs shared by map.hip and abi.cpp. The public C ABI is include/m3s.h.
+// Internal (non-ABI) structs and launchers shared by map.hip and abi_map.cpp. The public C ABI is include/m3s.h.
 #pragma once
 #include <stdint.h>
 #include <hip/hip_runtime.h>
@@ -35,3 +35,8 @@ struct MapArgs {
   void* out;                // SOA: (M,3) f32; PLY: (M,15) bytes
   uint8_t* out_rgb;         // SOA: (M,3) u8 or null
 };
+
+extern "C" {
+hipError_t m3s_launch_map_count(const MapArgs* a, hipStream_t s);
+hipError_t m3s_launch_map_write(const MapArgs* a, hipStream_t s);
+}

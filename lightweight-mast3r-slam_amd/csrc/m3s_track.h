@@ -1,6 +1,8 @@
-// Internal (non-ABI) structs shared by track.hip and abi.cpp. The public C ABI is include/m3s.h.
+// Internal (non-ABI) structs, workspace constants and launchers shared by track.hip and abi_track.cpp. The public C
+// ABI is include/m3s.h.
 #pragma once
 #include <stdint.h>
+#include <hip/hip_runtime.h>
 
 #define M3S_TRACK_RUNNING 0
 #define M3S_TRACK_OK 1
@@ -14,6 +16,11 @@
 // shard's publish ticket when the GN launch publishes: {unique-match count : 32, stalled blocks : 16, arrivals : 16}
 // summed over the shard's blocks. The top publish ticket (M3S_TRACK_PUBLISH_TICKET, 64-bit there) has the same layout.
 #define M3S_TRACK_UNIQUE_WORD 1
+
+// The GN partial sums of the workspace: GN_SLOTS x GN_MAX_BLOCKS rows of GN_PSTRIDE doubles
+#define GN_PSTRIDE 40
+#define GN_SLOTS 64        // partial-sum slots of the persistent GN launch: one per iteration
+#define GN_MAX_BLOCKS 256  // partial rows per iteration slot: the GN launch's block cap
 
 // Device-resident GN state (one per tracked frame). Layout mirrored by m3s/_track.py (M3S_TRACK_STATE_*).
 struct TrackState {
@@ -106,3 +113,13 @@ struct FuseArgs {
   uint8_t* slot_dirty;
   int N_new, N_updates_new;
 };
+
+extern "C" {
+hipError_t m3s_launch_track_init(const TrackArgs* a, int N, hipStream_t s);
+hipError_t m3s_launch_track_setup(const TrackArgs* a, const TrackParams* p, hipStream_t s);
+int m3s_track_max_parts(void);  // blocks of the GN launch that can be resident at once on the current device
+hipError_t m3s_launch_track_iters(const TrackArgs* a, const TrackParams* p, int nparts, int fold,
+                                  const TrackPublish* pub, hipStream_t s);
+hipError_t m3s_launch_fuse(const TrackArgs* a, const FuseArgs* f, int count, int N, const TrackPublish* pub,
+                           hipStream_t s);
+}

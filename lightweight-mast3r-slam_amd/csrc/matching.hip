@@ -11,10 +11,7 @@
 // This file is compiled with -ffp-contract=off: the refine score must round every half product and
 // every half add separately (c10::Half operator* / operator+), which a contracted v_fma_f16 breaks.
 #include "m3s_proj.hpp"
-
-extern "C" hipError_t m3s_launch_refine_tile(const void*, const void*, const void*, void*, int, int, int, int, int,
-                                             int, int, void*, int*, const float*, hipStream_t);
-extern "C" int m3s_refine_tile_ok(int, int, int, int, int, int);
+#include "m3s_match.h"
 
 namespace m3s {
 
@@ -348,7 +345,7 @@ __global__ void __launch_bounds__(256) refine_f32_kernel(const float* __restrict
 }  // namespace m3s
 
 // ------------------------------------------------------------------------------------------
-// launchers (called from abi.cpp)
+// launchers (declared in m3s_match.h, called from abi_match.cpp)
 // ------------------------------------------------------------------------------------------
 // D11 (nullable): convert the descriptors too, planar (refine tile path, F = 24; cnorm_part nullable: the tile
 // partials of the screen's norm bound, B * tiles floats) or in the (B,H,W,F) layout (per-pixel refine kernels)

@@ -2,6 +2,8 @@
 // and an FMA loop on the box"). Not on the tracking / BA path.
 #include <hip/hip_runtime.h>
 
+#include "m3s_peaks.h"
+
 namespace m3s {
 
 // 8 independent v_fma_f32 chains per lane, `iters` rounds; 4 waves per SIMD at the launch below.

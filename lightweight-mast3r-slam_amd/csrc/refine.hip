@@ -35,6 +35,7 @@
 // (scripts/micro/fma_rates, profiles/r03_valu_issue_rates.txt): VOP2 f16 add 1.18 ns, SDWA / VOP3P / v_perm
 // 2.03-2.09 ns per wave-instruction, so 2.67 ns per channel-candidate against 3.1 ns paired: 125 -> 116 us.
 #include "m3s_proj.hpp"
+#include "m3s_match.h"
 
 namespace m3s {
 

@@ -34,6 +34,8 @@
 
 #include <type_traits>
 
+#include "m3s_retrieval.h"  // RQ_NQT, RQ_QG, RQ_ROWS and the launchers
+
 namespace m3s {
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
@@ -42,10 +44,7 @@ typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(1))) const void* rq_gptr;
 typedef __attribute__((address_space(3))) void* rq_lptr;
 
-#define RQ_NQT 19                 // query column tiles (16 queries) per group
-#define RQ_QG (RQ_NQT * 16)       // 304 queries per group
 #define RQ_NR 2                   // codebook row tiles (16 rows) per wave
-#define RQ_ROWS 256               // codebook rows per block: 8 waves x 32
 #define RQ_THREADS 512            // 8 waves
 #define RQ_NL 32                  // lane slots per query in a block: 8 waves x 4 lane groups
 #define RQ_BT (RQ_ROWS / 16)      // codebook row tiles per block

@@ -30,8 +30,6 @@
 namespace m3s {
 
 #define GN_NSUM 36
-#define GN_PSTRIDE 40
-#define GN_SLOTS 64  // partial-sum slots of the persistent GN launch: one per iteration
 
 // lietorch group product with the product quaternion re-normalised (RxSO3 ctor), float.
 __device__ __forceinline__ void sim3_mul_norm(const float* A, const float* B, float* C) {
@@ -410,7 +408,6 @@ typedef __attribute__((address_space(1))) unsigned long long gull;
 #ifndef GN_PAIR  // points in float2 pairs, fp32 product sums per thread (gn_pair) instead of fp64 FMAs per product
 #define GN_PAIR 1
 #endif
-#define GN_MAX_BLOCKS 256           // partial rows per iteration slot
 
 // ---- the 36 fp64 sums of a wave, reduce-scattered over its lanes (deterministic, no LDS) ----
 // Six half-exchange steps: lanes l and l^32 (v_permlane32_swap: the two halves of a register pair trade places,
@@ -1228,11 +1225,8 @@ __global__ void __launch_bounds__(256) fuse_kernel(const TrackState* __restrict_
 
 }  // namespace m3s
 
-extern "C" hipError_t m3s_launch_track_init(const TrackArgs* a, const float* T_WCf, const float* T_WCk, int N,
-                                            hipStream_t s) {
+extern "C" hipError_t m3s_launch_track_init(const TrackArgs* a, int N, hipStream_t s) {
   const int n16 = (N + 15) / 16;  // the byte map is carved with a 16-B padded length
-  (void)T_WCf;
-  (void)T_WCk;  // read by track_setup (TrackArgs)
   hipLaunchKernelGGL(m3s::track_init_kernel, dim3((n16 + 255) / 256), dim3(256), 0, s,
                      reinterpret_cast<uint4*>(a->flags), n16, a->cnt, a->tick);
   return hipGetLastError();
@@ -1265,15 +1259,13 @@ extern "C" int m3s_track_max_parts(void) {
   return n;
 }
 
-// one persistent launch runs every GN iteration (iters and chunk_id are kept for the call sites); fold: the setup
-// runs inside it (gn_loop_kernel<true>, no track_setup launch before it)
+// one persistent launch runs every GN iteration; fold: the setup runs inside it (gn_loop_kernel<true>, no track_setup
+// launch before it)
 // pub->mirror set (folded launches only): the launch also counts the unique matches and publishes the result, and the
 // fuse launch behind it gets no mirror and no count
-extern "C" hipError_t m3s_launch_track_iters(const TrackArgs* a, const TrackParams* p, int nparts, int iters,
-                                             int chunk_id, int fold, const TrackPublish* pub, hipStream_t s) {
-  (void)iters;
-  (void)chunk_id;
-  if (nparts < 1 || nparts > 256) return hipErrorInvalidValue;  // <= 32 blocks per XCD shard (the shard-last loads)
+extern "C" hipError_t m3s_launch_track_iters(const TrackArgs* a, const TrackParams* p, int nparts, int fold,
+                                             const TrackPublish* pub, hipStream_t s) {
+  if (nparts < 1 || nparts > GN_MAX_BLOCKS) return hipErrorInvalidValue;  // <= 32 blocks per XCD shard (the shard-last loads)
   if (!fold && pub->mirror != nullptr) return hipErrorInvalidValue;
   if (fold)
     hipLaunchKernelGGL(m3s::gn_loop_kernel<true>, dim3(nparts), dim3(GN_THREADS), 0, s, *a, *p, *pub);
@@ -1283,12 +1275,12 @@ extern "C" hipError_t m3s_launch_track_iters(const TrackArgs* a, const TrackPara
 }
 
 // fusion (f->X_in non-null) and/or the unique-match count (count: the state's n_unique from the byte
-// map) for the GN batch chunk_id that finished
-extern "C" hipError_t m3s_launch_fuse(const TrackArgs* a, int chunk_id, const FuseArgs* f, int count, int N,
-                                      const TrackPublish* pub, hipStream_t s) {
+// map); the kernel's chunk id (the GN batch that finished) is always 0: one persistent launch runs every iteration
+extern "C" hipError_t m3s_launch_fuse(const TrackArgs* a, const FuseArgs* f, int count, int N, const TrackPublish* pub,
+                                      hipStream_t s) {
   const int grid = (N + 255) / 256 > FUSE_COUNT_BLOCKS ? (N + 255) / 256 : FUSE_COUNT_BLOCKS;  // every counting block publishes
   // count: the byte map was written by track_setup (fused path), so it is counted and cleared
-  hipLaunchKernelGGL(m3s::fuse_kernel, dim3(grid), dim3(256), 0, s, a->state, chunk_id, *f, N, a->flags,
+  hipLaunchKernelGGL(m3s::fuse_kernel, dim3(grid), dim3(256), 0, s, a->state, 0, *f, N, a->flags,
                      count ? &a->state->n_unique : nullptr, *pub, count, a->tick, a->cnt);
   return hipGetLastError();
 }

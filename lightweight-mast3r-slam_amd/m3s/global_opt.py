@@ -169,73 +169,59 @@ class FactorGraph:
 
     def solve_GN_rays(self):
         """global_opt.py:123-161, with the keyframe points read in place (no torch.stack of K x N x 16 B)."""
-        cfg = self.cfg
-        pin = self._pin(cfg)
-        unique_kf_idx = self.get_unique_kf_idx()
-        if unique_kf_idx.numel() <= max(pin, 1):
-            return
-        ii, jj, idx_ii2jj, valid_match, Q_ii2jj = self.prep_two_way_edges()
-        rk = self._reuse_kw(unique_kf_idx)
-        zc = self.get_poses_keyframes(unique_kf_idx)
-        if zc is not None:
-            from m3s.dist_ba import gauss_newton_sharded
-
-            T_WCs, keyframes = zc
-            gauss_newton_sharded("rays", T_WCs.data[:, 0, :], None, None, ii, jj, idx_ii2jj, valid_match, Q_ii2jj,
-                                 cfg, cfg["max_iters"], cfg["delta_norm"],
-                                 group=self.group, keyframes=keyframes, **rk)
-            self.frames.update_T_WCs(T_WCs[pin:], unique_kf_idx[pin:])
-            return
-        Xs, T_WCs, Cs = self.get_poses_points(unique_kf_idx)
-        pose_data = T_WCs.data[:, 0, :]
-        if self._sharded() or rk:
-            from m3s.dist_ba import gauss_newton_sharded
-
-            gauss_newton_sharded("rays", pose_data, Xs, Cs, ii, jj, idx_ii2jj, valid_match, Q_ii2jj, cfg,
-                                 cfg["max_iters"], cfg["delta_norm"], group=self.group, **rk)
-        else:
-            mast3r_slam_backends.gauss_newton_rays(pose_data, Xs, Cs, ii, jj, idx_ii2jj, valid_match, Q_ii2jj,
-                                                   cfg["sigma_ray"], cfg["sigma_dist"], cfg["C_conf"], cfg["Q_conf"],
-                                                   cfg["max_iters"], cfg["delta_norm"])
-        self.frames.update_T_WCs(T_WCs[pin:], unique_kf_idx[pin:])
+        self._solve_GN("rays")
 
     def solve_GN_calib(self):
         """global_opt.py:163-226, with the keyframe points read in place: the raw-calib BA mode constrains them to
         their pixel rays in the kernels (bit-identical to constrain_points_to_ray on the stacked copy), so neither the
         torch.stack of K x N x 12 B, nor the pixel grid, nor the constrained copy is made. M3S_BA_CALIB_ZERO_COPY=0
         keeps the stacked path."""
+        self._solve_GN("calib")
+
+    def _solve_GN(self, mode):
+        """The flow both modes share: the keyframes in place where they qualify (calib: and _calib_zero_copy allows
+        it), else the stacked copy (calib: constrained to its pixel rays), solved sharded / with record reuse or by
+        the drop-in backend call."""
         cfg = self.cfg
-        K = self.K
+        calib = mode == "calib"
+        K = self.K if calib else None
         pin = self._pin(cfg)
         unique_kf_idx = self.get_unique_kf_idx()
         if unique_kf_idx.numel() <= max(pin, 1):
             return
-        img_size = frame_img_size(self.frames[0])
-        height, width = img_size
+        ckw = {}
+        if calib:
+            img_size = frame_img_size(self.frames[0])
+            height, width = img_size
+            ckw = {"K": K, "height": height, "width": width}
         ii, jj, idx_ii2jj, valid_match, Q_ii2jj = self.prep_two_way_edges()
         rk = self._reuse_kw(unique_kf_idx)
-        zc = self.get_poses_keyframes(unique_kf_idx) if self._calib_zero_copy(K) else None
+        zc = self.get_poses_keyframes(unique_kf_idx) if not calib or self._calib_zero_copy(K) else None
         if zc is not None:
             from m3s.dist_ba import gauss_newton_sharded
 
             T_WCs, keyframes = zc
-            gauss_newton_sharded("calib", T_WCs.data[:, 0, :], None, None, ii, jj, idx_ii2jj, valid_match, Q_ii2jj,
-                                 cfg, cfg["max_iters"], cfg["delta_norm"], K=K, height=height, width=width,
+            gauss_newton_sharded(mode, T_WCs.data[:, 0, :], None, None, ii, jj, idx_ii2jj, valid_match, Q_ii2jj,
+                                 cfg, cfg["max_iters"], cfg["delta_norm"], **ckw,
                                  group=self.group, keyframes=keyframes, **rk)
             self.frames.update_T_WCs(T_WCs[pin:], unique_kf_idx[pin:])
             return
         Xs, T_WCs, Cs = self.get_poses_points(unique_kf_idx)
-        Xs = constrain_points_to_ray(img_size, Xs, K)
+        if calib:
+            Xs = constrain_points_to_ray(img_size, Xs, K)
         pose_data = T_WCs.data[:, 0, :]
         if self._sharded() or rk:
             from m3s.dist_ba import gauss_newton_sharded
 
-            gauss_newton_sharded("calib", pose_data, Xs, Cs, ii, jj, idx_ii2jj, valid_match, Q_ii2jj, cfg,
-                                 cfg["max_iters"], cfg["delta_norm"], K=K, height=height, width=width,
-                                 group=self.group, **rk)
-        else:
+            gauss_newton_sharded(mode, pose_data, Xs, Cs, ii, jj, idx_ii2jj, valid_match, Q_ii2jj, cfg,
+                                 cfg["max_iters"], cfg["delta_norm"], **ckw, group=self.group, **rk)
+        elif calib:
             mast3r_slam_backends.gauss_newton_calib(pose_data, Xs, Cs, K, ii, jj, idx_ii2jj, valid_match, Q_ii2jj,
                                                     height, width, cfg["pixel_border"], cfg["depth_eps"],
                                                     cfg["sigma_pixel"], cfg["sigma_depth"], cfg["C_conf"],
                                                     cfg["Q_conf"], cfg["max_iters"], cfg["delta_norm"])
+        else:
+            mast3r_slam_backends.gauss_newton_rays(pose_data, Xs, Cs, ii, jj, idx_ii2jj, valid_match, Q_ii2jj,
+                                                   cfg["sigma_ray"], cfg["sigma_dist"], cfg["C_conf"], cfg["Q_conf"],
+                                                   cfg["max_iters"], cfg["delta_norm"])
         self.frames.update_T_WCs(T_WCs[pin:], unique_kf_idx[pin:])

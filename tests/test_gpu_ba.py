@@ -295,7 +295,7 @@ def test_ba_full_chunk_runs_vs_fp64_truth(mode, monkeypatch):
     inside the first run). Poses within 1e-5 of the oracle's fp64 truth."""
     from m3s.synthetic import make_graph, two_way
 
-    # the production chunk length of large graphs (small graphs get shorter chunks, abi.cpp ba_chunks)
+    # the production chunk length of large graphs (small graphs get shorter chunks, abi_ba.cpp ba_chunks)
     monkeypatch.setenv("M3S_BA_CHUNK_POINTS", "24576")
     H, W = 128, 192
     G = make_graph(n_kf=6, H=H, W=W, seed=11)

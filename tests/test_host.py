@@ -27,6 +27,43 @@ def test_abi_library_exports_every_declared_symbol():
     assert lib.m3s_abi_version() == hdr_version == _lib.ABI_VERSION
 
 
+def test_launchers_are_declared_once_in_a_header_their_definition_includes():
+    """Every function defined in one csrc file and called from another is declared in a header both include: an
+    extern "C" prototype copied by hand still links when it drifts from its definition, and passes wrong arguments."""
+    csrc = os.path.join(REPO, "lightweight-mast3r-slam_amd", "csrc")
+    text = {f: open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc))
+            if f.endswith((".hip", ".cpp", ".h"))}
+    sources = {f: t for f, t in text.items() if f.endswith((".hip", ".cpp"))}
+    headers = {f: t for f, t in text.items() if f.endswith(".h")}
+    assert sources and headers
+    # a prototype: the name, a parenthesised parameter list without braces or semicolons, then ';'. A preceding
+    # identifier character or '(' / ',' / operator makes it a call, so the return type's last character must precede it
+    proto = re.compile(r"(?:[\w\*&]\s+|\*)(m3s_[a-z0-9_]+)\s*\(([^;{}]*)\)\s*;")
+
+    def prototypes(t):
+        t = re.sub(r"//[^\n]*", "", t)
+        out = []
+        for m in proto.finditer(t):
+            line = t[t.rfind("\n", 0, m.start()) + 1:m.start() + 1]
+            if re.search(r"\breturn\b|[=(,?:!]", line):  # a call inside an expression or statement
+                continue
+            out.append(m.group(1))
+        return out
+
+    for f, t in sources.items():
+        assert prototypes(t) == [], f"{f} declares {prototypes(t)}: prototypes live in the headers"
+    launchers = {}
+    for f, t in sources.items():
+        if f.endswith(".hip"):
+            for name in re.findall(r'extern "C"\s+hipError_t\s+(m3s_launch_[a-z0-9_]+)\s*\([^;{}]*\)\s*\{', t):
+                launchers[name] = f
+    assert len(launchers) >= 20, sorted(launchers)
+    for name, f in sorted(launchers.items()):
+        where = [h for h, t in headers.items() if name in prototypes(t)]
+        assert len(where) == 1, f"{name} ({f}) is declared in {where}"
+        assert re.search(r'#include\s+"%s"' % re.escape(where[0]), sources[f]), f"{f} does not include {where[0]}"
+
+
 def test_workspace_sizes_are_monotone():
     from m3s import _lib
 
