@@ -22,7 +22,7 @@
 extern "C" {
 #endif
 
-#define M3S_ABI_VERSION 7
+#define M3S_ABI_VERSION 8
 
 #define M3S_OK 0
 #define M3S_EINVAL -1  /* bad shape / argument (reference: TORCH_CHECK -> RuntimeError) */
@@ -38,7 +38,8 @@ const char* m3s_last_error(void);
 /* Per-kernel HIP-event timing (no reference counterpart; the reference's profiler.py wraps regions
  * with torch.cuda.synchronize). When enabled, every launch group is bracketed by hipEvents on its
  * own stream under a name: prep_rays, proj_occlusion, refine_lin, track_setup, gn_iters,
- * ba_linearize, ba_solve, map_count, map_write. query synchronises the recorded events. (m3s_match runs the
+ * ba_linearize, ba_solve, map_count, map_write, quantize_topk, asmk_update (the whole fused call, the
+ * quantiser's span inside it). query synchronises the recorded events. (m3s_match runs the
  * projection search inside the refine launch where the tile path is taken: refine_lin then covers both and
  * proj_occlusion has no spans, count 0; M3S_MATCH_FUSE_PROJ=0 separates them.) */
 void m3s_timing_enable(int on);
@@ -287,6 +288,70 @@ int m3s_codebook_prepare(const float* centroids, int C, int D, void* codebook, s
 size_t m3s_quantize_workspace_size(int C, int D, int M, int k);
 int m3s_quantize(const void* codebook, int C, int D, const float* qvecs, int M, int k, int64_t* topk_out,
                  void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- retrieval: the device-resident ASMK database (aggregate, score, top-k, append) ----
+ * Replaces everything RetrievalDatabase.update does after prep_features (retrieval_database.py:43-72, 107-166) for the
+ * configuration mast3r/retrieval/processor.py:91-96 fixes: binary kernel, use_idf False (other configurations are
+ * rejected by the caller; nothing here falls back to the host).
+ *   aggregate  asmk/kernel.py:26-39 + cython/hamming.pyx:24-30,79-109: for every unique word of the first `use_cols`
+ *              columns of ids (M, k) int64, the fp32 sum over its rows (ascending, a row once) of
+ *              fp32(des[row] - centroid[word]); bit = sum > 0, packed MSB-first (dim d -> word d / 32, bit 31 - d % 32).
+ *              Codes are bit-exact with the reference. Words come out sorted; *count stays on the device.
+ *   search     asmk/inverted_file.py:86-108, kernel.py:56-68, functional.py:11-15: for every query word and database
+ *              entry of the same word h = popcount(q ^ e), sim = fp32(-2 fp32(h / D) + 1), kept if
+ *              sim >= similarity_threshold, term = fp32(fp64(powf(sim, alpha)) / sqrt(fp64(norm[image]))), summed in
+ *              fp64 per image and divided by sqrt(number of unique query words). norm[image] is the image's entry
+ *              count. The sum's order is fixed (identical from run to run) but not the inverted file's.
+ *   add        inverted_file.py:56-76, retrieval_database.py:138-166: append (code, word) under image id n_images.
+ *   update     retrieval_database.py:43-72: quantise with k_query, aggregate, search, torch.topk(min(k, n_images)) with
+ *              the `> min_thresh` filter (ties -> lower image index), then, with add_after_query, aggregate the first
+ *              k_build columns again and append. On an empty database there is no query (count 0) and the add
+ *              quantises with k_build (:149-154).
+ * The database is a forward file in one device buffer: the (D + 1)-entry table of powf(sim, alpha), entries in
+ * insertion order (codes (max_entries, D / 32) u32, words i32), img_ptr (max_images + 1) entry offsets, norm and the
+ * fp64 scores of the last query. init fills the section pointers of the descriptor, uploads the table and empties the
+ * database; n_images and entries_bound (an upper bound of the entries used: the host never reads a device count) are
+ * host bookkeeping that add / update advance. M3S_ESPACE: the database cannot take another image of M * k_build
+ * entries (nothing was launched; grow and repeat) or the workspace is short.
+ * Limits: D % 32 == 0, M * k <= 4096, M <= 4096, C <= 2^20, 1 <= k_build <= k_query <= 8, k <= 64. Word ids must lie
+ * in 0 .. C-1 (the quantiser's do). Everything is asynchronous on `stream`. */
+#define M3S_ASMK_MAX_TOPK 64
+typedef struct m3s_asmk_db {
+  void* buf; /* device, m3s_asmk_db_size bytes */
+  size_t bytes;
+  int D, max_images;
+  int64_t max_entries;
+  int n_images;          /* host bookkeeping */
+  int64_t entries_bound; /* host bookkeeping */
+  /* sections of buf, set by init */
+  float* table;
+  uint32_t* codes;
+  int32_t* words;
+  int32_t* img_ptr;
+  int32_t* norm;
+  double* scores; /* (max_images): the last query's scores of images 0 .. n_images-1 */
+} m3s_asmk_db;
+typedef struct m3s_asmk_result { /* device; read back once by the caller */
+  int32_t count;
+  int32_t idx[M3S_ASMK_MAX_TOPK];
+  double score[M3S_ASMK_MAX_TOPK];
+} m3s_asmk_result;
+size_t m3s_asmk_db_size(int D, int max_images, int64_t max_entries);
+int m3s_asmk_db_init(m3s_asmk_db* db /* host; buf, bytes, D, max_images, max_entries set by the caller */, float alpha,
+                     float similarity_threshold, void* stream);
+size_t m3s_asmk_workspace_size(int C, int D, int M, int k);
+/* codes (M * use_cols, D / 32) u32, words (M * use_cols) i32, count (1) i32: the first *count rows are valid */
+int m3s_asmk_aggregate(const float* centroids, int C, int D, const float* features, int M, const int64_t* ids, int k,
+                       int use_cols, uint32_t* codes, int32_t* words, int32_t* count, void* workspace,
+                       size_t workspace_bytes, void* stream);
+/* scores (n_images) f64; max_q: the rows the query arrays hold (<= 4096) */
+int m3s_asmk_search(const m3s_asmk_db* db, const uint32_t* q_codes, const int32_t* q_words, const int32_t* q_count,
+                    int max_q, double* scores, void* stream);
+int m3s_asmk_add(m3s_asmk_db* db, const uint32_t* codes, const int32_t* words, const int32_t* count, int max_count,
+                 void* stream);
+int m3s_asmk_update(const void* codebook, const float* centroids, int C, m3s_asmk_db* db, const float* features, int M,
+                    int k_query, int k_build, int k, double min_thresh, int add_after_query,
+                    m3s_asmk_result* result /* device */, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- map export: the confidence-filtered world point cloud of the keyframes ----
  * Replaces the per-keyframe host loop of evaluate.save_reconstruction (mast3r_slam/evaluate.py:47-70, called at

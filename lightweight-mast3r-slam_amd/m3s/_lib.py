@@ -14,7 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # M3S_LIB: alternative build of the same library (kernel experiments); still the HIP library, no fallback
 LIB_PATH = os.environ.get("M3S_LIB") or os.path.join(os.path.dirname(_HERE), "lib", "libm3s.so")
 
-ABI_VERSION = 7  # include/m3s.h M3S_ABI_VERSION
+ABI_VERSION = 8  # include/m3s.h M3S_ABI_VERSION
 
 c_int, c_float, c_double, c_size_t, c_void_p = ctypes.c_int, ctypes.c_float, ctypes.c_double, ctypes.c_size_t, ctypes.c_void_p
 
@@ -73,6 +73,20 @@ class TrackResult(ctypes.Structure):
                 ("N", c_int)]
 
 
+class AsmkDb(ctypes.Structure):
+    _fields_ = [("buf", c_void_p), ("bytes", c_size_t), ("D", c_int), ("max_images", c_int),
+                ("max_entries", ctypes.c_int64), ("n_images", c_int), ("entries_bound", ctypes.c_int64),
+                ("table", c_void_p), ("codes", c_void_p), ("words", c_void_p), ("img_ptr", c_void_p),
+                ("norm", c_void_p), ("scores", c_void_p)]
+
+
+ASMK_MAX_TOPK = 64
+
+
+class AsmkResult(ctypes.Structure):
+    _fields_ = [("count", ctypes.c_int32), ("idx", ctypes.c_int32 * ASMK_MAX_TOPK), ("score", c_double * ASMK_MAX_TOPK)]
+
+
 TRACK_OK, TRACK_MAX_ITERS, TRACK_CHOLESKY_FAILED, TRACK_SKIPPED = 1, 2, 3, 4
 
 # exported entry points and their argtypes (restype int unless noted)
@@ -127,6 +141,15 @@ _SIGS = {
     "m3s_codebook_prepare": ([c_void_p, c_int, c_int, c_void_p, c_size_t, c_void_p], c_int),
     "m3s_quantize_workspace_size": ([c_int] * 4, c_size_t),
     "m3s_quantize": ([c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p], c_int),
+    "m3s_asmk_db_size": ([c_int, c_int, ctypes.c_int64], c_size_t),
+    "m3s_asmk_db_init": ([ctypes.POINTER(AsmkDb), c_float, c_float, c_void_p], c_int),
+    "m3s_asmk_workspace_size": ([c_int] * 4, c_size_t),
+    "m3s_asmk_aggregate": ([c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p,
+                            c_void_p, c_void_p, c_size_t, c_void_p], c_int),
+    "m3s_asmk_search": ([ctypes.POINTER(AsmkDb), c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p], c_int),
+    "m3s_asmk_add": ([ctypes.POINTER(AsmkDb), c_void_p, c_void_p, c_void_p, c_int, c_void_p], c_int),
+    "m3s_asmk_update": ([c_void_p, c_void_p, c_int, ctypes.POINTER(AsmkDb), c_void_p, c_int, c_int, c_int, c_int,
+                         c_double, c_int, c_void_p, c_void_p, c_size_t, c_void_p], c_int),
     "m3s_track": ([ctypes.POINTER(TrackInputs), ctypes.POINTER(TrackConfig), ctypes.POINTER(TrackFuse), c_int,
                    c_void_p, ctypes.POINTER(TrackResult), c_void_p, c_size_t, c_void_p], c_int),
 }

@@ -9,7 +9,11 @@ spawned backend process of ``main.py``):
   constructors, methods and returns), so ``from mast3r_slam.tracker import FrameTracker`` in ``main.py:29`` (and
   ``:17``) binds the fused classes;
 * ``mast3r_slam.config.config`` becomes ``m3s.config.config`` (one dict, which the reference's ``load_config``
-  updates in place: ``config.py:41-44``), so the fused classes read the YAML the run was started with.
+  updates in place: ``config.py:41-44``), so the fused classes read the YAML the run was started with;
+* ``mast3r_slam.retrieval_database.RetrievalDatabase`` becomes a subclass of itself with
+  ``m3s.retrieval.DatabaseMixin`` in front (``SUBCLASSES``), so ``load_retriever`` (``mast3r_utils.py:50-57``, which
+  imports the name from that module) builds a database whose ``update`` runs on the device; the retrieval model and
+  ``prep_features`` stay the reference's.
 
 Nothing of the reference is copied or edited; without the hook directory on the path nothing changes.
 """
@@ -20,11 +24,13 @@ import sys
 PATCHES = {"mast3r_slam.config": ("config", "m3s.config"),
            "mast3r_slam.tracker": ("FrameTracker", "m3s.tracker"),
            "mast3r_slam.global_opt": ("FactorGraph", "m3s.global_opt")}
+# module -> (its class, the module and name of the mixin put in front of it)
+SUBCLASSES = {"mast3r_slam.retrieval_database": ("RetrievalDatabase", "m3s.retrieval", "DatabaseMixin")}
 
 
 class _PatchingFinder(importlib.abc.MetaPathFinder):
     def find_spec(self, name, path, target=None):
-        if name not in PATCHES:
+        if name not in PATCHES and name not in SUBCLASSES:
             return None
         for finder in sys.meta_path:
             if finder is self or not hasattr(finder, "find_spec"):
@@ -34,7 +40,6 @@ class _PatchingFinder(importlib.abc.MetaPathFinder):
                 break
         else:
             return None
-        attr, src = PATCHES[name]
         loader = spec.loader
         orig_exec = loader.exec_module
 
@@ -44,7 +49,14 @@ class _PatchingFinder(importlib.abc.MetaPathFinder):
 
             def exec_module(self, module):
                 orig_exec(module)
-                setattr(module, attr, getattr(importlib.import_module(src), attr))
+                if name in PATCHES:
+                    attr, src = PATCHES[name]
+                    setattr(module, attr, getattr(importlib.import_module(src), attr))
+                else:
+                    attr, src, mixin = SUBCLASSES[name]
+                    base = getattr(module, attr)
+                    setattr(module, attr, type(attr, (getattr(importlib.import_module(src), mixin), base),
+                                               {"__module__": base.__module__, "__doc__": base.__doc__}))
                 setattr(module, "_m3s_original_" + attr, True)
 
         spec.loader = _Loader()

@@ -257,6 +257,48 @@ def retrieval_inputs(seed, C, D, M):
     return c, q
 
 
+def asmk_sequence(seed, C, D, M, n_images, margin=1e-3, k=8):
+    """A codebook and a sequence of images for the ASMK database: unit-norm fp32 centroids (C, D) and local
+    features (n_images, M, D), each a centroid plus a direction that belongs to the word plus noise. Image i draws its
+    words from a window sliding over the codebook, so neighbouring images share words and score against each other.
+
+    With ``margin`` > 0 a feature is redrawn until its k + 1 smallest fp64 distances to the centroids are at least
+    ``margin`` apart, so that any quantiser accurate to well below ``margin`` assigns the same first k words in the
+    same order (the golden fixtures store the reference's word ids). ``margin=0`` skips the distances: the timing
+    workload's codebook is too large for them."""
+    rng = np.random.default_rng(seed)
+    c = rng.standard_normal((C, D)).astype(np.float32)
+    c /= np.linalg.norm(c, axis=1, keepdims=True)
+    u = rng.standard_normal((C, D)).astype(np.float32)
+    u /= np.linalg.norm(u, axis=1, keepdims=True)
+    width = max(4, min(C, 3 * C // 8))
+    step = max(1, width // 6)
+    words = np.stack([(i * step + rng.integers(0, width, size=M)) % C for i in range(n_images)])
+
+    def draw(w):
+        g = rng.standard_normal((len(w), D)).astype(np.float32)
+        g /= np.linalg.norm(g, axis=1, keepdims=True)
+        return (c[w] + np.float32(0.35) * u[w] + np.float32(0.35) * g).astype(np.float32)
+
+    w = words.reshape(-1)
+    f = draw(w)
+    if margin > 0:
+        kk = min(k + 1, C)
+        c64 = c.astype(np.float64)
+        cn = np.sum(c64 * c64, axis=1)
+        todo = np.arange(len(w))
+        for _ in range(200):
+            q = f[todo].astype(np.float64)
+            l2 = (np.sum(q * q, axis=1)[:, None] + cn[None, :]) - 2.0 * (q @ c64.T)
+            near = np.sort(np.partition(l2, kk - 1, axis=1)[:, :kk], axis=1)
+            todo = todo[np.diff(near, axis=1).min(axis=1) < margin]
+            if len(todo) == 0:
+                break
+            f[todo] = draw(w[todo])
+        assert len(todo) == 0, "asmk_sequence: could not separate the nearest centroids"
+    return c, f.reshape(n_images, M, D)
+
+
 # ------------------------------------------------------------------------------------------------
 # C4/C5 factor graphs on a recorded trajectory
 # ------------------------------------------------------------------------------------------------
