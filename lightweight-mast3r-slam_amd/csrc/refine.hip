@@ -29,6 +29,8 @@
 //     its slab of D11.
 //   * On the fused match path the same launch first runs the projection search for the tile's pixels (FUSE_PROJ,
 //     m3s_proj.hpp): no launch and no p1 round trip between the LM search and the levels.
+//   * Every block of a 512x512 launch is resident at once, so the waves' issue priority follows their progress
+//     (RT_PRIO_TABLE below: a wave a level behind the others on its SIMD outranks them) and the blocks finish together.
 // Compiled with -ffp-contract=off and -fno-slp-vectorize: each candidate's half sum stays a scalar chain (VOP2
 // v_add_f16 for the even channel, SDWA v_add_f16 for the odd one) instead of the SLP vectoriser pairing two
 // candidates per v_pk_add_f16 behind v_perm / v_pack transposes. Measured issue costs on gfx950 at 4 waves/SIMD
@@ -77,6 +79,58 @@ static_assert(3 * RT_PROWS * RT_PCOLS <= RT_ROWS * RT_COLS && 2 * RT_DROWS * RT_
 
 typedef __attribute__((address_space(1))) const void* gvoid_t;
 typedef __attribute__((address_space(3))) void* lvoid_t;
+
+// Wave issue priority (s_setprio, user priority 0..3: the SIMD's arbiter takes the highest priority first, then the
+// oldest wave). All 1024 blocks of a 512x512 launch are resident from the first microsecond, four per CU, so under
+// oldest-first alone the blocks dispatched last lose every issue conflict and the launch ends on them (block 75 us at
+// the median, launch 105 us). Two uses, both compile-time (RT_PRIO_TABLE; DESIGN section 4 refine has the measurements):
+//   * by phase: a block's chain alternates short issue phases that each start a long latency (the ~10 DMA rows of a
+//     fill, a survivor trip's six loads, the LM gathers, the level-start exchange three other waves wait for) with long
+//     dot2 bursts that start none. LM: the FUSE_PROJ instance's projection search and the D21 row loads behind it;
+//     START: the level-start bbox reduction with its two barriers (and the window outliers' in-place levels); FILL: the
+//     window fills through their vmcnt(0) and barrier arrival; SURV: the loads of an exact_survivors trip; SCORE:
+//     screen_chunk / score_chunk, the mask and the exact chains.
+//   * by level (LAG, "laggards first"): every value falls by one per level below d = 3, so a wave that is a level
+//     behind the others on its SIMD outranks them in every phase and the blocks finish together.
+// The shipped table 3 does both; by level alone (4) measured the same median with more spread, by phase alone (1, 2)
+// a quarter of the gain. The kernel has no spin-wait, so priorities change neither results nor liveness. An all-zero
+// table emits no s_setprio at all.
+#ifndef RT_PRIO_TABLE
+#define RT_PRIO_TABLE 3
+#endif
+// columns: LM, START, FILL, SURV, SCORE, LAG
+#if RT_PRIO_TABLE == 0  // none: oldest-first
+#define RT_PRIO_ROW 0, 0, 0, 0, 0, 0
+#elif RT_PRIO_TABLE == 1  // the latency-starting phases over the bursts
+#define RT_PRIO_ROW 3, 3, 3, 3, 0, 0
+#elif RT_PRIO_TABLE == 2  // the same, the LM phase left at the default
+#define RT_PRIO_ROW 0, 3, 3, 3, 0, 0
+#elif RT_PRIO_TABLE == 3  // laggards first: 3 / 2 (latency phases / bursts) at d >= 3, 2 / 1 at d = 2, 1 / 0 at d = 1
+#define RT_PRIO_ROW 3, 3, 3, 3, 2, 1
+#elif RT_PRIO_TABLE == 4  // laggards first by level alone: 3 at d >= 3, 2 at d = 2, 1 at d = 1
+#define RT_PRIO_ROW 3, 3, 3, 3, 3, 1
+#else
+#error "RT_PRIO_TABLE: 0..4"
+#endif
+constexpr int RT_PRIO_TAB[6] = {RT_PRIO_ROW};
+constexpr int RT_PRIO_LM = RT_PRIO_TAB[0], RT_PRIO_START = RT_PRIO_TAB[1], RT_PRIO_FILL = RT_PRIO_TAB[2],
+              RT_PRIO_SURV = RT_PRIO_TAB[3], RT_PRIO_SCORE = RT_PRIO_TAB[4], RT_PRIO_LAG = RT_PRIO_TAB[5];
+constexpr bool RT_PRIO_ON =
+    (RT_PRIO_LM | RT_PRIO_START | RT_PRIO_FILL | RT_PRIO_SURV | RT_PRIO_SCORE | RT_PRIO_LAG) != 0;
+// the priority of phase value p at level d (d = 0: outside the levels)
+constexpr int rt_prio_at(int p, int d) {
+  const int q = (RT_PRIO_LAG && d > 0 && d < 3) ? p - (3 - d) : p;
+  return q < 0 ? 0 : (q > 3 ? 3 : q);
+}
+template <int P, int D = 0>
+__device__ __forceinline__ void rt_prio() {
+  if constexpr (RT_PRIO_ON) __builtin_amdgcn_s_setprio(rt_prio_at(P, D));
+}
+// ... where the wave is known to run at phase value FROM: nothing to do when the two are equal
+template <int FROM, int P, int D>
+__device__ __forceinline__ void rt_prio_from() {
+  if constexpr (RT_PRIO_ON && rt_prio_at(FROM, D) != rt_prio_at(P, D)) __builtin_amdgcn_s_setprio(rt_prio_at(P, D));
+}
 
 #ifdef M3S_REFINE_STATS  // (experiment builds only) per-level deferred lanes / waves
 __device__ unsigned long long g_refine_stats[64];
@@ -158,8 +212,14 @@ __device__ __forceinline__ void score_chunk(const uint4* base, const h2* q4, h1*
 //   * After the first level the centre candidate (3,3) is the last winner (its score IS the running max) or the
 //     start pixel that did not beat +0: it never wins a strict '>' and is dropped from the survivors.
 //   * |q| cmax > 16384 (overflow range) or non-finite: every in-image candidate survives (exact for all).
+// seed (chunk 0, a constant at every call site): a[] is written, not accumulated into. The candidate's first product
+// starts from +0 (0 + x: the same bits as accumulating into a zeroed register), so the 49 accumulators are not live
+// in front of chunk 0: zeroed ahead of the fill barrier they cost 98 moves per level (49 to zero them, 49 more where
+// the screen's branch re-materialised them), now the one v_mov 0 the compiler puts in front of each candidate's first
+// two-operand v_dot2c. (It selects v_dot2c for fdot2(q, c, 0) whatever the zero's source; the three-operand
+// v_dot2_f32_f16 with an inline 0 would need inline asm and hand-kept dot -> VALU wait states.)
 template <int D, int STRIDE = RT_COLS>
-__device__ __forceinline__ void screen_chunk(const uint4* base, const h2* q4, float* a) {
+__device__ __forceinline__ void screen_chunk(const uint4* base, const h2* q4, float* a, bool seed = false) {
   constexpr int G = 7;
 #pragma unroll
   for (int i = 0; i < G; i++) {
@@ -176,7 +236,7 @@ __device__ __forceinline__ void screen_chunk(const uint4* base, const h2* q4, fl
 #pragma unroll
       for (int j = j0; j < min(G, j0 + RT_COLBATCH); j++) {
         const h2* cv = reinterpret_cast<const h2*>(&c[j - j0]);
-        float t = a[i * G + j];
+        float t = seed ? 0.0f : a[i * G + j];
 #pragma unroll
         for (int k = 0; k < 4; k++) t = __builtin_amdgcn_fdot2(q4[k], cv[k], t, false);
         a[i * G + j] = t;
@@ -225,6 +285,7 @@ __device__ __forceinline__ void exact_survivors(const h1* __restrict__ img, int 
     const int cb = m != 0 ? __ffsll((long long)m) - 1 : -1;
     m &= m - 1;
     uint4 a0, a1, a2, b0, b1, b2;
+    rt_prio_from<RT_PRIO_SCORE, RT_PRIO_SURV, D>();  // the trip's loads start an L2 round trip
     if (ca >= 0) {
       const int i = ca / 7, j = ca - 7 * i;
       load_chunks<PLANAR>(pix_ptr<PLANAR>(img, (size_t)(v_lo + j * D) * W + (u_lo + i * D)), (size_t)H * W, a0, a1,
@@ -235,6 +296,7 @@ __device__ __forceinline__ void exact_survivors(const h1* __restrict__ img, int 
       load_chunks<PLANAR>(pix_ptr<PLANAR>(img, (size_t)(v_lo + j * D) * W + (u_lo + i * D)), (size_t)H * W, b0, b1,
                           b2);
     }
+    rt_prio_from<RT_PRIO_SURV, RT_PRIO_SCORE, D>();
     if (ca >= 0) {
       h1 sc = (h1)0.0f;
       add8(sc, &q[0], a0);
@@ -310,6 +372,7 @@ __device__ __forceinline__ void refine_level(const TileCtx& t, bool& active, con
                                              h1& max_score, uint4* lds, int (*s_red)[4], bool first) {
   constexpr int R = 3, G = 2 * R + 1, F = 24, RD = R * D;
   const int lane = t.lane, wid = t.wid, H = t.H, W = t.W;
+  rt_prio<RT_PRIO_START, D>();  // three other waves wait at the exchange's barriers
   // bbox of the inlier centres (within 16 px of pixel + the tile's flow estimate t.fu/t.fv)
   const bool inl = active && abs(cu - t.u_pix - t.fu) <= 16 && abs(cv - t.v_pix - t.fv) <= 16;
   int mnu = inl ? cu : INT_MAX, mxu = inl ? cu : INT_MIN;
@@ -416,10 +479,13 @@ __device__ __forceinline__ void refine_level(const TileCtx& t, bool& active, con
   const int lane_off = gx * (PLANAR ? 8 : F);
   const size_t cstride = PLANAR ? (size_t)H * W * 8 : 8, rstride = (size_t)W * (PLANAR ? 8 : F);
   if constexpr (SCREEN) {
-    float a[G * G];
+    float a[G * G];  // written by chunk 0's screen (seed): no zeroing
+#ifdef RT_NOCOMP
 #pragma unroll
     for (int c = 0; c < G * G; c++) a[c] = 0.0f;
+#endif
     __syncthreads();  // the reduction scratch aliases the window: its readers are done
+    rt_prio_from<RT_PRIO_START, RT_PRIO_FILL, D>();
     if (packed) {  // (d = 1 only) the three chunk planes in one fill
 #ifndef RT_NOLOAD
       for (int r = wid; r < 3 * nrows; r += RT_WAVES) {
@@ -433,10 +499,11 @@ __device__ __forceinline__ void refine_level(const TileCtx& t, bool& active, con
 #endif
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       __syncthreads();
+      rt_prio_from<RT_PRIO_FILL, RT_PRIO_SCORE, D>();
 #ifndef RT_NOCOMP
       if (lane_in) {
         const int b0 = by * RT_PCOLS + bx;
-        screen_chunk<D, RT_PCOLS>(&lds[b0], &q[0], a);
+        screen_chunk<D, RT_PCOLS>(&lds[b0], &q[0], a, true);
         screen_chunk<D, RT_PCOLS>(&lds[RT_PPLANE + b0], &q[4], a);
         screen_chunk<D, RT_PCOLS>(&lds[2 * RT_PPLANE + b0], &q[8], a);
       }
@@ -460,24 +527,32 @@ __device__ __forceinline__ void refine_level(const TileCtx& t, bool& active, con
       __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0) expcnt(7) lgkmcnt(15)
       __syncthreads();
       fill(1, RT_DBUF);
+      rt_prio_from<RT_PRIO_FILL, RT_PRIO_SCORE, D>();
 #ifndef RT_NOCOMP
-      if (lane_in) screen_chunk<D, RT_PCOLS>(&lds[b0], &q[0], a);
+      if (lane_in) screen_chunk<D, RT_PCOLS>(&lds[b0], &q[0], a, true);
 #endif
+      rt_prio_from<RT_PRIO_SCORE, RT_PRIO_FILL, D>();
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       __syncthreads();  // chunk 1 landed; every wave is done with buffer 0
       fill(2, 0);
+      rt_prio_from<RT_PRIO_FILL, RT_PRIO_SCORE, D>();
 #ifndef RT_NOCOMP
       if (lane_in) screen_chunk<D, RT_PCOLS>(&lds[RT_DBUF + b0], &q[4], a);
 #endif
+      rt_prio_from<RT_PRIO_SCORE, RT_PRIO_FILL, D>();
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       __syncthreads();
+      rt_prio_from<RT_PRIO_FILL, RT_PRIO_SCORE, D>();
 #ifndef RT_NOCOMP
       if (lane_in) screen_chunk<D, RT_PCOLS>(&lds[b0], &q[8], a);
 #endif
     } else {
 #pragma unroll
       for (int chunk = 0; chunk < F / 8; chunk++) {
-        if (chunk) __syncthreads();
+        if (chunk) {
+          rt_prio_from<RT_PRIO_SCORE, RT_PRIO_FILL, D>();
+          __syncthreads();
+        }
 #ifndef RT_NOLOAD
         for (int y = wid; y < nrows; y += RT_WAVES) {
           const int gy = min(max(wy0 + y, 0), H - 1);
@@ -488,8 +563,9 @@ __device__ __forceinline__ void refine_level(const TileCtx& t, bool& active, con
 #endif
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
+        rt_prio_from<RT_PRIO_FILL, RT_PRIO_SCORE, D>();
 #ifndef RT_NOCOMP
-        if (lane_in) screen_chunk<D>(&lds[by * RT_COLS + bx], &q[chunk * 4], a);
+        if (lane_in) screen_chunk<D>(&lds[by * RT_COLS + bx], &q[chunk * 4], a, chunk == 0);
 #endif
       }
     }
@@ -506,10 +582,22 @@ __device__ __forceinline__ void refine_level(const TileCtx& t, bool& active, con
 #pragma unroll
         for (int c = 0; c < G * G; c++) a[c] = ((vm >> c) & 1ull) ? a[c] : -INFINITY;
       }
+      // the level's best over the candidates that can win: after the first level the centre is dropped from the
+      // survivors (below), and it cannot raise T either: its exact score is the running max or a start pixel's <= +0,
+      // so a[centre] - 2B <= max_score - B, the other term of T
       float lmax = a[0];
 #pragma unroll
-      for (int c = 1; c < G * G; c++) lmax = fmaxf(lmax, a[c]);
-      const float T = fmaxf((float)max_score - t.bq, lmax - 2.0f * t.bq);
+      for (int c = 1; c < G * G; c++)
+        if (c != G * G / 2) lmax = fmaxf(lmax, a[c]);
+      lmax = fmaxf(lmax, first ? a[G * G / 2] : -INFINITY);
+      // No lane of the wave can hold a survivor: the mask, the survivor loop and the re-centre are skipped as one
+      // wave-uniform branch. A lane's mask is non-empty exactly when lmax >= max_score - B: lmax is one of its
+      // candidates' a[c] and never below lmax - 2B, so it clears T = max(max_score - B, lmax - 2B) iff it clears the
+      // first term, and no candidate clears a T that lmax does not (a NaN lmax fails both tests). A lane without a
+      // usable bound (!sok: every candidate survives) keeps the wave out of the skip.
+      const float tms = (float)max_score - t.bq;
+      if (__builtin_amdgcn_readfirstlane((int)(__ballot(!t.sok || lmax >= tms) != 0ull)) == 0) return;
+      const float T = fmaxf(tms, lmax - 2.0f * t.bq);
       uint64_t m = screen_mask(a, T);
       if (!t.sok) m = ~0ull;
       m &= vm;
@@ -547,9 +635,13 @@ __device__ __forceinline__ void refine_level(const TileCtx& t, bool& active, con
 #pragma unroll
   for (int c = 0; c < G * G; c++) s[c] = (h1)0.0f;
   __syncthreads();  // the reduction scratch aliases the window: its readers are done
+  rt_prio_from<RT_PRIO_START, RT_PRIO_FILL, D>();
 #pragma unroll
   for (int chunk = 0; chunk < F / 8; chunk++) {
-    if (chunk) __syncthreads();  // previous chunk's readers are done
+    if (chunk) {
+      rt_prio_from<RT_PRIO_SCORE, RT_PRIO_FILL, D>();
+      __syncthreads();  // previous chunk's readers are done
+    }
 #ifndef RT_NOLOAD
     for (int y = wid; y < nrows; y += RT_WAVES) {  // one global_load_lds (64 lanes x 16 B) per window row
       const int gy = min(max(wy0 + y, 0), H - 1);
@@ -559,6 +651,7 @@ __device__ __forceinline__ void refine_level(const TileCtx& t, bool& active, con
 #endif
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
+    rt_prio_from<RT_PRIO_FILL, RT_PRIO_SCORE, D>();
 #ifndef RT_NOCOMP
     if (lane_in) score_chunk<D>(&lds[by * RT_COLS + bx], &q[chunk * 4], s);
 #endif
@@ -695,6 +788,8 @@ __global__ void __launch_bounds__(RT_THREADS, RT_MIN_BLOCKS) refine_tile_kernel(
   float4 dv[F / 4];   // FUSE_PROJ: the raw D21 row, converted where it is first needed
   float cmax_w = 0.0f;  // FUSE_PROJ && SCREEN: the descriptor-norm bound, held by wave 0 until the tile-flow exchange
   if constexpr (FUSE_PROJ) {
+    // the LM gathers and the D21 row loads behind them (until the first level's start sets its own)
+    rt_prio_from<0, RT_PRIO_LM, 0>();
     // a lane past the image projects the nearest pixel inside it (every address stays in bounds, no branch join in
     // front of the loads) and writes nothing
     const int n = min(t.v_pix, H - 1) * W + min(t.u_pix, W - 1);
@@ -825,6 +920,7 @@ __global__ void __launch_bounds__(RT_THREADS, RT_MIN_BLOCKS) refine_tile_kernel(
   RT_LEVEL(2)
   RT_LEVEL(1)
 #undef RT_LEVEL
+  rt_prio<0>();
   if (mine && active) store_out<LIN_OUT>(outv, bn, W, cu, cv);
 #ifdef M3S_REFINE_BSTAMPS
   const unsigned long long nact = __popcll(__ballot(active));
