@@ -271,7 +271,8 @@ typedef struct m3s_track_result {
 size_t m3s_track_workspace_size(int N);
 int m3s_track_release(const void* workspace);
 int m3s_track(const m3s_track_inputs* in, const m3s_track_config* cfg, const m3s_track_fuse_args* fuse,
-              int first_chunk, float* T_out_dev /* (16) nullable: T_WCf | T_CkCf on device */,
+              int first_chunk /* ignored: one persistent launch runs every GN iteration */,
+              float* T_out_dev /* (16) nullable: T_WCf | T_CkCf on device */,
               m3s_track_result* result /* host */, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- retrieval codebook quantization ----

@@ -219,7 +219,7 @@ extern "C" int m3s_track(const m3s_track_inputs* in, const m3s_track_config* cfg
     Span sp("track_setup", s);
     HIP_TRY(m3s_launch_track_setup(&a, &p, s), "track setup launch");
   }
-  (void)first_chunk;  // every GN iteration runs inside one persistent launch (gn_loop_kernel)
+  (void)first_chunk;  // ignored (include/m3s.h)
   const int nparts = std::min(track_nparts(N), m3s_track_max_parts());  // every block co-resident
   TrackMirror* mirror = pinned_mirror();
   if (mirror == nullptr) return fail(M3S_EHIP, "track: pinned result mirror allocation failed");

@@ -39,8 +39,6 @@ constexpr bool ba_is_calib(int mode) { return mode == BA_MODE_CALIB || mode == B
 // ------------------------------------------------------------------------------------------
 // linearisation
 // ------------------------------------------------------------------------------------------
-typedef float f2 __attribute__((ext_vector_type(2)));
-
 // MASK: the row's structurally nonzero Jacobian entries (bit c). Products with a structural zero are skipped:
 // for finite weights they add an exact +-0 to the sum, so the result is unchanged (the reference computes
 // them; ~45% of the FMAs in rays mode). Products and sums in fp32 (packed: two points per instruction) over
@@ -123,16 +121,6 @@ __device__ __forceinline__ f2 BA_FMA2(f2 a, f2 b, f2 c) {
 #else
   return a * b + c;
 #endif
-}
-
-// actSO3 of two points (component arrays), same expression as actSO3
-__device__ __forceinline__ void actSO3_v(const float* q, const f2* X, f2* Y) {
-  const f2 uv0 = 2.0f * (q[1] * X[2] - q[2] * X[1]);
-  const f2 uv1 = 2.0f * (q[2] * X[0] - q[0] * X[2]);
-  const f2 uv2 = 2.0f * (q[0] * X[1] - q[1] * X[0]);
-  Y[0] = X[0] + q[3] * uv0 + (q[1] * uv2 - q[2] * uv1);
-  Y[1] = X[1] + q[3] * uv1 + (q[2] * uv0 - q[0] * uv2);
-  Y[2] = X[2] + q[3] * uv2 + (q[0] * uv1 - q[1] * uv0);
 }
 
 // The fp64 accumulation is split between the two lanes of a lane pair (even lane: sums 0..17, odd lane: 18..34). At
@@ -566,7 +554,7 @@ __global__ void __launch_bounds__(256, BA_LIN_WAVES) ba_lin_kernel(BaArgs a, BaP
                                                    __builtin_elementwise_fma(f2{M[3 * c + 2], M[3 * c + 2]}, Xj[2],
                                                                              f2{Tij[c], Tij[c]})));
 #else
-    actSO3_v(&Tij[3], Xj, Y);  // actSim3 (gn_kernels.cu:207-219): rotate, scale, translate
+    actSO3_2(&Tij[3], Xj, Y);  // actSim3 (gn_kernels.cu:207-219): rotate, scale, translate
 #pragma unroll
     for (int c = 0; c < 3; c++) Y[c] = Y[c] * Tij[7] + Tij[c];
 #endif

@@ -38,6 +38,29 @@ __device__ __forceinline__ void actSim3(const float* T, const float* X, float* Y
   Y[2] = Y[2] * T[7] + T[2];
 }
 
+// actSO3 / actSim3 of two points at once (component arrays of float2 lanes, packed fp32 instructions): the same
+// expressions elementwise, so each point rounds as in the scalar functions
+typedef float f2 __attribute__((ext_vector_type(2)));
+
+__device__ __forceinline__ void actSO3_2(const float* q, const f2* X, f2* Y) {
+  const f2 uv0 = 2.0f * (q[1] * X[2] - q[2] * X[1]);
+  const f2 uv1 = 2.0f * (q[2] * X[0] - q[0] * X[2]);
+  const f2 uv2 = 2.0f * (q[0] * X[1] - q[1] * X[0]);
+  const f2 y0 = X[0] + q[3] * uv0 + (q[1] * uv2 - q[2] * uv1);
+  const f2 y1 = X[1] + q[3] * uv1 + (q[2] * uv0 - q[0] * uv2);
+  const f2 y2 = X[2] + q[3] * uv2 + (q[0] * uv1 - q[1] * uv0);
+  Y[0] = y0;
+  Y[1] = y1;
+  Y[2] = y2;
+}
+
+__device__ __forceinline__ void actSim3_2(const float* T, const f2* X, f2* Y) {
+  actSO3_2(&T[3], X, Y);
+  Y[0] = Y[0] * T[7] + T[0];
+  Y[1] = Y[1] * T[7] + T[1];
+  Y[2] = Y[2] * T[7] + T[2];
+}
+
 // T_ij = T_i^-1 T_j   (gn_kernels.cu:252-272)
 __device__ __forceinline__ void relSim3(const float* Ti, const float* Tj, float* Tij) {
   const float si_inv = 1.0f / Ti[7];

@@ -22,7 +22,7 @@
 #define GN_SLOTS 64        // partial-sum slots of the persistent GN launch: one per iteration
 #define GN_MAX_BLOCKS 256  // partial rows per iteration slot: the GN launch's block cap
 
-// Device-resident GN state (one per tracked frame). Layout mirrored by m3s/_track.py (M3S_TRACK_STATE_*).
+// Device-resident GN state (one per tracked frame). The host reads a copy of it from TrackMirror.
 struct TrackState {
   float T[8];      // T_CkCf (current estimate)
   float T_WCk[8];  // keyframe pose
@@ -35,7 +35,6 @@ struct TrackState {
   int n_valid_opt;
   int n_valid_kf;
   int n_unique;
-  int done_chunk;  // host chunk id of the GN launch batch that finished (gates the fuse launch)
 };
 
 struct TrackParams {

@@ -116,7 +116,6 @@ class FrameTracker:
         self.model = model
         self.keyframes = frames
         self.device = device
-        self.first_chunk = 8  # GN iterations enqueued before the first host readback
         self.last_result = None
         # fuse straight into a buffer-backed store's slot (SharedKeyframes) instead of tracker.py:101's full-record
         # copy; False: the reference's copy (A/B tests and the bench's comparison leg)
@@ -274,11 +273,9 @@ class FrameTracker:
         res = _lib.TrackResult()
         st = _lib.stream_ptr(dev)
         ws = _lib.workspace("track", lib.m3s_track_workspace_size(N), dev, st)
-        _lib.check(lib.m3s_track(ctypes.byref(ins), ctypes.byref(tc), ctypes.byref(fz), int(self.first_chunk),
+        _lib.check(lib.m3s_track(ctypes.byref(ins), ctypes.byref(tc), ctypes.byref(fz), 0,
                                  T_out.data_ptr(), ctypes.byref(res), ws.data_ptr(), ws.numel(), st))
         self.last_result = res
-        if not direct:  # next frame: enqueue as many GN launches as this one needed (+1) before reading back
-            self.first_chunk = max(2, min(int(tc.max_iters), res.iters + 1))
         return res, T_f, T_r
 
     # ------------------------------------------------------------------ reference method surface

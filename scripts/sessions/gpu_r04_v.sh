@@ -1,5 +1,5 @@
 #!/bin/bash
-# round 4: GN point pairs with fp32 product sums (GN_PAIR=1, shipped) vs fp64 product FMAs (lib/exp/libm3s_gnf64.so):
+# round 4: GN point pairs with fp32 product sums (shipped) vs fp64 product FMAs (lib/exp/libm3s_gnf64.so):
 # tracking parity tests, then the tracking bench A/B (three alternating pairs)
 set -o pipefail
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/../..}"

@@ -318,8 +318,8 @@ def _track_once(g, mode, H, W, cfg):
 def test_track_folded_setup_bit_identical(golden, monkeypatch, case):
     """M3S_TRACK_FOLD_SETUP=1 (setup inside the GN launch's first iteration, the skip test after its hand-off) gives
     the separate-setup path's result bit for bit: decisions, iterations, status, counts, pose, cost, fused points and
-    confidences. track.hip is built without FMA contraction (csrc/Makefile FLAGS_track), so the shared setup_point /
-    track_state_init code rounds the same in both instantiations."""
+    confidences. track.hip is built without FMA contraction (csrc/Makefile FLAGS_track), so the shared setup_points /
+    initial_T_CkCf code rounds the same in both instantiations."""
     from m3s.config import reset_config
 
     g = golden("tracking_48x64.npz")
