@@ -22,7 +22,7 @@
 extern "C" {
 #endif
 
-#define M3S_ABI_VERSION 8
+#define M3S_ABI_VERSION 9
 
 #define M3S_OK 0
 #define M3S_EINVAL -1  /* bad shape / argument (reference: TORCH_CHECK -> RuntimeError) */
@@ -38,7 +38,7 @@ const char* m3s_last_error(void);
 /* Per-kernel HIP-event timing (no reference counterpart; the reference's profiler.py wraps regions
  * with torch.cuda.synchronize). When enabled, every launch group is bracketed by hipEvents on its
  * own stream under a name: prep_rays, proj_occlusion, refine_lin, track_setup, gn_iters,
- * ba_linearize, ba_solve, map_count, map_write, quantize_topk, asmk_update (the whole fused call, the
+ * ba_linearize, ba_solve, map_count, map_voxel, map_write, quantize_topk, asmk_update (the whole fused call, the
  * quantiser's span inside it). query synchronises the recorded events. (m3s_match runs the
  * projection search inside the refine launch where the tile path is taken: refine_lin then covers both and
  * proj_occlusion has no spans, count 0; M3S_MATCH_FUSE_PROJ=0 separates them.) */
@@ -391,6 +391,27 @@ int m3s_map_count(const m3s_map_config* cfg, const m3s_ba_keyframes* kf, int Kp,
 int m3s_map_write(const m3s_map_config* cfg, const m3s_ba_keyframes* kf, const float* Twc, const uint8_t* const* rgb,
                   int Kp, int N, void* out, uint8_t* out_rgb, int64_t capacity, void* workspace, size_t workspace_bytes,
                   void* stream);
+/* Voxel-grid thinning, between m3s_map_count and m3s_map_write on the same workspace: of the counted rows, one per
+ * occupied voxel stays in the stored mask. The world point y of a row is the write's (the same device code); with
+ * r = float32(1) / float32(voxel_size) its voxel is q_c = floorf(y_c * r) per coordinate (one fp32 multiply, one floor).
+ * A row whose y is not finite, or with a q_c outside [-2^20, 2^20), is dropped and counted. Per voxel the row with the
+ * largest average confidence C_k[n] * float32(1 / N_avg[k]) survives, among equal confidences the smallest global
+ * index g = k N + n (k the position in the keyframe table): its own point and colour, no centroid, so the result is
+ * bit-reproducible. Survivors keep the export's order, so the thinned output is a subsequence of the unfiltered one;
+ * m3s_map_write then runs unchanged (its header and capacity checks see the thinned total).
+ * table: device memory of at least m3s_map_voxel_table_size(total of the count) bytes, 16-byte aligned; an
+ * open-addressing hash table of 16-byte (key, best) slots, cleared here. m3s_map_voxel_table_size: 16 B times a power
+ * of two of slots >= 2 total, at least 1024; 0 for a negative or overflowing total.
+ * Uploads the keyframe pointer tables and the ray tables through the workspace, runs insert, thin and the count's scan,
+ * and synchronises the stream. counts_out (host, Kp, nullable) / total_out (host): the thinned rows; dropped_out
+ * (host, nullable): valid rows that reached no voxel (not finite, out of range, or a point that changed during the call).
+ * M3S_EINVAL: voxel_size not finite or <= 0, a null table, Kp N >= 2^32, no count preceded on this workspace or its
+ * Kp / N / threshold differ (the mask is then left as it was); M3S_ESPACE: short workspace, or table_bytes below the
+ * size for the counted total. */
+size_t m3s_map_voxel_table_size(int64_t total);
+int m3s_map_voxel(const m3s_map_config* cfg, const m3s_ba_keyframes* kf, const float* Twc, int Kp, int N,
+                  float voxel_size, void* table, size_t table_bytes, int64_t* counts_out, int64_t* total_out,
+                  int64_t* dropped_out, void* workspace, size_t workspace_bytes, void* stream);
 
 /* Measured-peak probe (no reference counterpart; bench.py's roofline context):
  * blocks x 256 lanes x iters x 8 chains of v_fma_f32 (2 flops each) on `stream`. */

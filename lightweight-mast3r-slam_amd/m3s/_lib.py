@@ -14,7 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # M3S_LIB: alternative build of the same library (kernel experiments); still the HIP library, no fallback
 LIB_PATH = os.environ.get("M3S_LIB") or os.path.join(os.path.dirname(_HERE), "lib", "libm3s.so")
 
-ABI_VERSION = 8  # include/m3s.h M3S_ABI_VERSION
+ABI_VERSION = 9  # include/m3s.h M3S_ABI_VERSION
 
 c_int, c_float, c_double, c_size_t, c_void_p = ctypes.c_int, ctypes.c_float, ctypes.c_double, ctypes.c_size_t, ctypes.c_void_p
 
@@ -132,6 +132,10 @@ _SIGS = {
                       c_int),
     "m3s_map_write": ([ctypes.POINTER(MapConfig), ctypes.POINTER(BaKeyframes), c_void_p, ctypes.POINTER(c_void_p),
                        c_int, c_int, c_void_p, c_void_p, ctypes.c_int64, c_void_p, c_size_t, c_void_p], c_int),
+    "m3s_map_voxel_table_size": ([ctypes.c_int64], c_size_t),
+    "m3s_map_voxel": ([ctypes.POINTER(MapConfig), ctypes.POINTER(BaKeyframes), c_void_p, c_int, c_int, c_float,
+                       c_void_p, c_size_t, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64),
+                       ctypes.POINTER(ctypes.c_int64), c_void_p, c_size_t, c_void_p], c_int),
     "m3s_peak_fma_f32": ([c_void_p, c_int, c_int, c_void_p], c_int),
     "m3s_match_workspace_size": ([c_int] * 4, c_size_t),
     "m3s_match": ([c_void_p] * 7 + [c_int] * 5 + [c_float] * 3 + [c_int, c_int, c_void_p, c_size_t, c_void_p], c_int),

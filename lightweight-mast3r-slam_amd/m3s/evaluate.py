@@ -6,7 +6,9 @@ the end of a run (``evaluate.save_reconstruction``, ``main.py:370-376``) and its
 ``T_WC.act``, three ``.cpu().numpy()`` copies, a boolean index and a final concatenate). Here the keyframes' own
 device buffers are read in place by two HIP passes (csrc/map.hip: ``m3s_map_count`` stores one validity bit per point
 and scans the block counts, ``m3s_map_write`` transforms and compacts in keyframe order and pixel order), so only the
-poses (K x 8 floats) and the colours (3 B per pixel, the host ``uimg``) are gathered.
+poses (K x 8 floats) and the colours (3 B per pixel, the host ``uimg``) are gathered. ``voxel_size`` adds one stage
+between the passes (``m3s_map_voxel``) that thins the cloud to one row per occupied voxel; ``voxel_select`` states its
+rule in torch ops.
 
 ``world_points_torch`` is the same contract in plain torch ops, the reference's formulation on
 ``m3s.geometry.constrain_points_to_ray`` and ``Sim3.act``; it runs on any device and is what ``world_points`` falls
@@ -15,6 +17,7 @@ differing sizes).
 """
 import ctypes
 import pathlib
+import warnings
 
 import numpy as np
 import torch
@@ -60,28 +63,87 @@ def _pack_ply(points, colors):
     return torch.cat((xyz, rgb), dim=1)
 
 
-def world_points_torch(keyframes, c_conf_threshold, indices=None, colors=True, layout="soa"):
+_VOXEL_RANGE = float(1 << 20)  # voxel coordinates lie in [-2^20, 2^20): csrc/m3s_map.h MAP_VOX_RANGE
+
+
+def _voxel_scale(voxel_size):
+    """float32(1) / float32(voxel_size), the one factor both paths multiply by."""
+    v = np.float32(voxel_size)
+    if not (np.isfinite(v) and v > 0):
+        raise ValueError(f"voxel_size must be finite and positive, not {voxel_size!r}")
+    return float(np.float32(1) / v)
+
+
+def _voxel_pick(points, conf, voxel_size):
+    """``voxel_select`` and the number of rows that reached no voxel."""
+    points, conf = points.reshape(-1, 3), conf.reshape(-1)
+    r = torch.tensor(_voxel_scale(voxel_size), dtype=torch.float32, device=points.device)
+    q = torch.floor(points.to(torch.float32) * r)  # one fp32 multiply, one floor
+    ok = torch.isfinite(points).all(dim=1) & ((q >= -_VOXEL_RANGE) & (q < _VOXEL_RANGE)).all(dim=1)
+    rows = torch.nonzero(ok).flatten()
+    b = q[rows].to(torch.int64) + (1 << 20)  # 21 biased bits per coordinate
+    _, voxel = torch.unique((b[:, 0] << 42) | (b[:, 1] << 21) | b[:, 2], return_inverse=True)
+    # lexicographic pick by stable sorts, last key first: voxel, then confidence descending, then row ascending
+    by_conf = torch.sort(conf[rows], descending=True, stable=True).indices
+    order = by_conf[torch.sort(voxel[by_conf], stable=True).indices]
+    v = voxel[order]
+    first = torch.ones_like(v, dtype=torch.bool)
+    first[1:] = v[1:] != v[:-1]
+    return torch.sort(rows[order[first]]).values, int(points.shape[0] - rows.numel())
+
+
+def voxel_select(points, conf, voxel_size):
+    """The voxel-grid thinning rule of the map export, in plain torch ops on any device: the reference for
+    ``m3s_map_voxel``. ``points`` (M,3) f32 world points, ``conf`` (M) their average confidences. Returns the kept row
+    indices (int64, ascending).
+
+    With ``r = float32(1) / float32(voxel_size)`` the voxel of a row is ``floor(points * r)`` per coordinate (one fp32
+    multiply, one floor). A row with a non-finite coordinate, or a voxel coordinate outside ``[-2^20, 2^20)``, is
+    left out. Per occupied voxel one row is kept: the largest confidence, among equal confidences the smallest row
+    index. The rows themselves are kept (no centroid), so the result is exact and reproducible."""
+    return _voxel_pick(points, conf, voxel_size)[0]
+
+
+def _warn_dropped(dropped):
+    if dropped:
+        warnings.warn(f"world_points: {int(dropped)} rows dropped by the voxel grid (not finite, or outside 2^20 "
+                      "voxels of the origin)", RuntimeWarning, stacklevel=3)
+
+
+def world_points_torch(keyframes, c_conf_threshold, indices=None, colors=True, layout="soa", voxel_size=None):
     """``world_points`` in plain torch ops on the keyframes' device (evaluate.py:50-68 per keyframe, concatenated
-    there instead of on the host)."""
+    there instead of on the host); with ``voxel_size`` its rows are thinned by ``voxel_select``."""
     if layout not in _LAYOUTS:
         raise ValueError(f"world_points: layout must be 'soa' or 'ply', not {layout!r}")
+    if voxel_size is not None:
+        _voxel_scale(voxel_size)
     frames = _select(keyframes, indices)
     dev = frames[0].X_canon.device if frames else torch.device("cpu")
     use_calib, K = _intrinsics(keyframes, frames) if frames else (False, None)
     pts, cols, counts = [torch.zeros((0, 3), dtype=torch.float32, device=dev)], [], []
+    confs = [torch.zeros((0,), dtype=torch.float32, device=dev)]
     for kf in frames:
         X = kf.X_canon.reshape(-1, 3)
         if use_calib:
             X = constrain_points_to_ray(frame_img_size(kf), X[None], K.to(X.device))[0]
         pW = kf.T_WC.to(X.device).act(X).reshape(-1, 3)
-        valid = kf.get_average_conf().reshape(-1) > c_conf_threshold
+        conf = kf.get_average_conf().reshape(-1)
+        valid = conf > c_conf_threshold
         pts.append(pW[valid])
+        confs.append(conf[valid].to(dev, torch.float32))
         counts.append(int(valid.sum()))
         if colors:
             cols.append(_colors_u8(kf).to(dev)[valid])
     points = torch.cat(pts, dim=0)
     cols_t = torch.cat([torch.zeros((0, 3), dtype=torch.uint8, device=dev)] + cols, dim=0) if colors else None
     counts_t = torch.tensor(counts, dtype=torch.int64, device=dev)
+    if voxel_size is not None:
+        keep, dropped = _voxel_pick(points, torch.cat(confs), voxel_size)
+        owner = torch.repeat_interleave(torch.arange(len(frames), device=dev), counts_t)
+        counts_t = torch.bincount(owner[keep], minlength=len(frames))
+        points = points[keep]
+        cols_t = cols_t[keep] if colors else None
+        _warn_dropped(dropped)
     if layout == "ply":
         return _pack_ply(points, cols_t), counts_t
     return points, cols_t, counts_t
@@ -140,7 +202,25 @@ def map_write(mc, table, Twc, rgb_list, Kp, N, out, out_rgb, capacity, ws, devic
                                  _lib.ptr(out_rgb), int(capacity), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(device)))
 
 
-def world_points(keyframes, c_conf_threshold, indices=None, colors=True, layout="soa"):
+def map_voxel_table_size(total):
+    """``m3s_map_voxel_table_size``: bytes of the voxel table for a counted total."""
+    return int(_lib.load(require_gpu=False).m3s_map_voxel_table_size(int(total)))
+
+
+def map_voxel(mc, table, Twc, Kp, N, voxel_size, vox_table, ws, device):
+    """``m3s_map_voxel`` on torch's current stream, between ``map_count`` and ``map_write`` on ``ws``; ``vox_table``: a
+    uint8 device tensor of ``map_voxel_table_size(total)`` bytes or more. Returns (thinned rows per keyframe (Kp,)
+    int64 numpy, thinned total, rows dropped)."""
+    lib = _lib.load()
+    counts = (ctypes.c_int64 * Kp)()
+    total, dropped = ctypes.c_int64(), ctypes.c_int64()
+    _lib.check(lib.m3s_map_voxel(ctypes.byref(mc), ctypes.byref(table), _lib.ptr(Twc), Kp, N, float(voxel_size),
+                                 _lib.ptr(vox_table), vox_table.numel(), counts, ctypes.byref(total),
+                                 ctypes.byref(dropped), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(device)))
+    return np.frombuffer(counts, dtype=np.int64).copy(), int(total.value), int(dropped.value)
+
+
+def world_points(keyframes, c_conf_threshold, indices=None, colors=True, layout="soa", voxel_size=None):
     """The keyframes' points with average confidence above ``c_conf_threshold``, in the world frame.
 
     ``keyframes``: a ``Keyframes`` or ``SharedKeyframes`` store; ``indices`` selects and orders the keyframes
@@ -154,12 +234,21 @@ def world_points(keyframes, c_conf_threshold, indices=None, colors=True, layout=
     The poses are stacked to (K,8) as ``FactorGraph.get_poses_keyframes`` does; points and confidences are read where
     they live. ``uimg`` is on the host: it is converted as the reference does, ``(uimg * 255)`` truncated to u8, and
     uploaded at 3 B per pixel. Keyframes whose buffers do not qualify (not on a HIP device, not contiguous fp32,
-    differing N) go through ``world_points_torch``."""
+    differing N) go through ``world_points_torch``.
+
+    ``voxel_size`` (default None: every row) thins the cloud to one row per occupied cell of that size in the world
+    frame, by the rule of ``voxel_select``: the row with the largest average confidence, among equal ones the first in
+    the order above (so ties go to the first listed keyframe); the rows are a subsequence of the unthinned ones and
+    ``counts`` are the thinned counts. One stage between the two passes (``m3s_map_voxel``: a hash table of 16 B per
+    slot, 2 to 4 slots per counted row, cached like the workspace). Rows that are not finite or lie beyond 2^20 cells
+    of the origin are left out, with one ``RuntimeWarning`` naming their number."""
     if layout not in _LAYOUTS:
         raise ValueError(f"world_points: layout must be 'soa' or 'ply', not {layout!r}")
+    if voxel_size is not None:
+        _voxel_scale(voxel_size)
     frames = _select(keyframes, indices)
     if not frames or not _in_place_ok(frames):
-        return world_points_torch(keyframes, c_conf_threshold, indices, colors, layout)
+        return world_points_torch(keyframes, c_conf_threshold, indices, colors, layout, voxel_size)
     dev = frames[0].X_canon.device
     Kp, N = len(frames), frames[0].C.numel()
     use_calib, K = _intrinsics(keyframes, frames)
@@ -169,14 +258,20 @@ def world_points(keyframes, c_conf_threshold, indices=None, colors=True, layout=
         lib = _lib.load()
         ws = _lib.workspace("map", lib.m3s_map_workspace_size(Kp, N), dev, _lib.stream_ptr(dev))
         counts, M = map_count(mc, table, Kp, N, ws, dev)
+        Twc = None
+        if M > 0:
+            Twc = torch.stack([kf.T_WC.data.reshape(1, 8) for kf in frames])[:, 0, :]
+            Twc = Twc.to(dev, torch.float32).contiguous()
+        if voxel_size is not None and M > 0:
+            vox = _lib.workspace("map_voxel", lib.m3s_map_voxel_table_size(M), dev, _lib.stream_ptr(dev))
+            counts, M, dropped = map_voxel(mc, table, Twc, Kp, N, voxel_size, vox, ws, dev)
+            _warn_dropped(dropped)
         if layout == "ply":
             out, out_rgb = torch.empty((M, 15), dtype=torch.uint8, device=dev), None
         else:
             out = torch.empty((M, 3), dtype=torch.float32, device=dev)
             out_rgb = torch.empty((M, 3), dtype=torch.uint8, device=dev) if colors else None
         if M > 0:
-            Twc = torch.stack([kf.T_WC.data.reshape(1, 8) for kf in frames])[:, 0, :]
-            Twc = Twc.to(dev, torch.float32).contiguous()
             rgb = None
             if colors:  # one upload for all keyframes
                 rgb = torch.stack([_colors_u8(kf) for kf in frames]).to(dev).contiguous()
@@ -214,13 +309,14 @@ def save_ply(filename, points, colors):
     _write_ply(filename, pcd.view(np.uint8).reshape(-1, 15))
 
 
-def save_reconstruction(savedir, filename, keyframes, c_conf_threshold):
+def save_reconstruction(savedir, filename, keyframes, c_conf_threshold, voxel_size=None):
     """evaluate.py:47-70 through the PLY layout: the file is the header plus one device-to-host copy of the vertex
     records. Unlike the reference it does not overwrite ``keyframe.X_canon`` with the ray-constrained copy in calib
-    mode (evaluate.py:55-58): the keyframes are left as they are."""
+    mode (evaluate.py:55-58): the keyframes are left as they are. ``voxel_size`` thins the cloud as in
+    ``world_points``."""
     savedir = pathlib.Path(savedir)
     savedir.mkdir(exist_ok=True, parents=True)
-    records, _ = world_points(keyframes, c_conf_threshold, layout="ply")
+    records, _ = world_points(keyframes, c_conf_threshold, layout="ply", voxel_size=voxel_size)
     _write_ply(savedir / filename, records.cpu().numpy())
 
 
