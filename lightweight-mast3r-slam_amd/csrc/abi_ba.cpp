@@ -1,6 +1,7 @@
 // C ABI of libm3s.so (include/m3s.h): bundle adjustment. The plan (rank remap, record reuse, linearisation table,
 // one upload), the symbolic worker (assembly pattern, factor schedule), and the linearise / solve entry points.
-// Kernels live in ba.hip and ba_dense.hip, the pattern analysis in ba_pattern.cpp.
+// Kernels live in ba.hip (linearisation), ba_sparse.hip and ba_dense.hip (the solves), the pattern analysis in
+// ba_pattern.cpp.
 #include "abi_common.h"
 
 #include <algorithm>
@@ -308,20 +309,15 @@ int build_symbolic(PlanSym* Y, std::vector<int> ri, std::vector<int> rj, int E, 
   const int lmax = std::min(S.nlev + 1, BA_MAX_WIDE_STEPS);
   const bool flow_on = env_flag("M3S_BA_FLOW", true);  // M3S_BA_FLOW=0 (A/B experiments): level-synchronous loops
   std::vector<int> sched;
-  // bytes the one-workgroup dataflow kernel stages in LDS for a schedule (m3s_launch_ba_solve's test): the loop
-  // tables col_ptr .. sidx (sections 1-9, 16-B aligned as packed below) + the schedule, x (8 doubles per column) and
-  // 3 flags per column. A plan whose dataflow schedule does not fit runs level-synchronously.
+  // the loop tables col_ptr .. sidx (sections 1-9, 16-B aligned as packed below): with the schedule behind them, the
+  // plan bytes of the one-workgroup kernel's LDS rule (m3s_ba.h ba_sp_lds_bytes)
   size_t table_bytes = 0;
   {
     const std::vector<int>* t[9] = {&S.col_ptr, &S.lev_ptr, &S.lev_col, &S.grp_ptr, &S.grp, &S.pull_grp, &S.src,
                                     &S.sidx, &S.rowL};
     for (const std::vector<int>* v : t) table_bytes += (sizeof(int) * v->size() + 15) & ~(size_t)15;
   }
-  auto flow_fits = [&](const std::vector<int>& sc) {
-    const size_t plan = table_bytes + sizeof(int) * sc.size();
-    return ((plan + 15) & ~(size_t)15) + (size_t)S.nb * 64 + (size_t)S.nb * 12 <= (size_t)m3s::SP_PLAN_BYTES;
-  };
-  auto legacy_split = [&]() {  // launched wide steps: minimise the measured step costs
+  auto launch_cost_split = [&]() {  // launched wide steps: minimise the measured step costs
     constexpr double kLaunchUs = 5.8, kRoundUs = 3.7;
     std::vector<double> suffix(lmax + 1, 0.0);  // cost of steps [L, lmax) inside the workgroup
     for (int l = lmax - 1; l >= 0; l--)
@@ -344,7 +340,7 @@ int build_symbolic(PlanSym* Y, std::vector<int> ri, std::vector<int> rj, int E, 
       if (tasks[l] > thr) last = l;
     Y->wide_steps = std::min(last + 1, BA_MAX_WIDE_STEPS);
   } else {
-    Y->wide_steps = legacy_split();
+    Y->wide_steps = launch_cost_split();
   }
   // the wide steps' task records (ba_sparse_step_kernel): per task {j, b0, b1, pull group or -1} and its group's
   // source range, so a launched task starts with its column's own loads
@@ -367,7 +363,9 @@ int build_symbolic(PlanSym* Y, std::vector<int> ri, std::vector<int> rj, int E, 
   // dataflow schedule of the one-workgroup part and the back substitution (ba_pattern.h)
   if (flow_on) ba_flow_schedule(S, Y->wide_steps, M3S_BA_SP_WAVES, &sched);
   Y->flow = sched.empty() ? 0 : 1;
-  if (Y->flow && !flow_fits(sched)) {  // the kernel would run level-synchronously: drop the schedule (and say so)
+  // a schedule that does not fit the LDS instance: the kernel would run level-synchronously, so drop it (and say so)
+  const size_t flow_lds = m3s::ba_sp_lds_bytes(table_bytes + sizeof(int) * sched.size(), S.nb, true);
+  if (Y->flow && flow_lds > (size_t)m3s::SP_PLAN_BYTES) {
     Y->flow = 0;
     sched.clear();
   }

@@ -1,6 +1,6 @@
 // Dense fp64 Cholesky of the BA pose system (fallback for fill-heavy graphs).
 //
-// The block-sparse factorisation (ba.hip, ba_sparse_factor_kernel) runs down the elimination tree inside
+// The block-sparse factorisation (ba_sparse.hip, ba_sparse_factor_kernel) runs down the elimination tree inside
 // one workgroup; on graphs whose fill makes the factor nearly dense (e.g. loop closures to random earlier
 // keyframes) its level count and update volume approach the dense case, and this multi-CU dense
 // factorisation is faster. The plan picks one of the two from the symbolic factorisation (abi_ba.cpp).
@@ -10,13 +10,13 @@
 // Layout: H is ((2n+1) x n) row-major, n = 7 (K-1): rows 0..n-1 the system (lower triangle used), row n
 // the rhs g^T, rows n+1.. an identity carried through the factorisation (-> L^-T, so the back
 // substitution is one parallel mat-vec).
-#include "m3s_common.hpp"
-#include "m3s_ba.h"
+#include "m3s_ba.h"  // the launchers defined here
+#include "m3s_ba_dev.hpp"
 
 namespace m3s_dense {
+using m3s::bcast_lane;
+using m3s::rsqrt_nr;
 using m3s::wave_sum;
-
-#define BA_NSUM 36
 
 // assembly of the dense system from the plan's per-factor-block contribution CSR (blocks of the
 // permuted system; block (rowL[b], column j) -> H rows 7 rowL[b].., columns 7 j..), rhs rows and the
@@ -30,15 +30,11 @@ __global__ void __launch_bounds__(64) dense_assemble_kernel(BaArgs a, int n, int
     if (i < n) a.H[(size_t)(n + 1 + i) * n + i] = 1.0;
     return;
   }
-  const int* ptr = b < nL ? a.asm_ptr + b : a.rhs_ptr + (b - nL);
-  const int* ent = b < nL ? a.asm_ent : a.rhs_ent;
   int li;
+  if (!m3s::ba_asm_element(b, nL, t, &li)) return;
   double* out;
   if (b < nL) {
-    if (t >= 49) return;
     const int rr = t / 7, cc = t - 7 * (t / 7);
-    const int lo = min(rr, cc), hi = max(rr, cc);
-    li = lo * 7 - lo * (lo - 1) / 2 + (hi - lo);
     const int r = a.rowL[b];
     int j = 0;  // the column of block b: col_ptr[j] <= b < col_ptr[j+1]
     int lo_j = 0, hi_j = a.nb;
@@ -50,17 +46,9 @@ __global__ void __launch_bounds__(64) dense_assemble_kernel(BaArgs a, int n, int
     j = lo_j;
     out = a.H + (size_t)(r * 7 + rr) * n + j * 7 + cc;
   } else {
-    if (t >= 7) return;
-    li = 28 + t;
     out = a.H + (size_t)n * n + (b - nL) * 7 + t;
   }
-  double s = 0.0;
-  const int kb = ptr[0], ke = ptr[1];
-  for (int k = kb; k < ke; k++) {
-    const int e = ent[k];
-    s += ((e & 1) ? -1.0 : 1.0) * a.edge_sums[(size_t)(e >> 1) * BA_NSUM + li];
-  }
-  *out = s;
+  *out = m3s::ba_asm_sum(a, b, nL, li);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -86,29 +74,7 @@ __global__ void __launch_bounds__(64) dense_assemble_kernel(BaArgs a, int n, int
 
 typedef double d4v __attribute__((ext_vector_type(4)));
 
-// lanes of one wave exchanging data through LDS: a compiler memory barrier (the hardware returns a
-// wave's LDS accesses in order)
-__device__ __forceinline__ void wave_sync() {
-  asm volatile("" ::: "memory");
-  __builtin_amdgcn_wave_barrier();
-}
-
-__device__ __forceinline__ double bcast_lane(double v, int src) {
-  int2 x = *reinterpret_cast<int2*>(&v);
-  x.x = __builtin_amdgcn_readlane(x.x, src);
-  x.y = __builtin_amdgcn_readlane(x.y, src);
-  return *reinterpret_cast<double*>(&x);
-}
-
-// 1/sqrt(d) and 1/d for d > 0: the v_rsq_f64 / v_rcp_f64 estimates (~2^-22 relative) refined by ONE
-// Newton step (~2^-44): the pivot chain is latency-bound (a dependent v_fma_f64 costs ~13 ns on gfx950,
-// measured by scripts/micro/mfma_f64.hip), and 1e-13 relative pivots are far inside the 1e-5 pose
-// contract (the LAPACK parity test bounds the solve at 2e-6 of the step).
-__device__ __forceinline__ double rsqrt_nr(double d) {
-  const double y = __builtin_amdgcn_rsq(d);
-  return fma(y, fma(-0.5 * d * y, y, 0.5), y);
-}
-
+// 1/d for d > 0, like rsqrt_nr (m3s_ba_dev.hpp): the v_rcp_f64 estimate refined by ONE Newton step
 __device__ __forceinline__ double rcp_nr(double d) {
   const double y = __builtin_amdgcn_rcp(d);
   return fma(y, fma(-d, y, 1.0), y);
@@ -126,7 +92,7 @@ __device__ __forceinline__ void diag_step(double (&r)[W], int lane, bool& bad) {
       bad = true;
       d = 1.0;
     }
-    const double inv = rsqrt_nr(d);  // serial chain: hardware estimate + two Newton steps
+    const double inv = rsqrt_nr(d);  // serial chain: hardware estimate + one Newton step
     const double sj = d * inv;
     // unconditional multiplier (a lane-dependent select here makes the allocator spill r[])
     const double l = r[J] * inv;
@@ -165,20 +131,12 @@ constexpr int LP = PNB + 2;   // LDS row pitch (doubles) of the panel arrays
 // on other XCDs anyway, and a launch that left ~28 MB of dirty trailing-matrix lines in L2 paid their
 // write-back at its end (the kernel boundary), on the critical path.
 __device__ __forceinline__ void st_wt(double* p, double v) {
-#ifdef M3S_CHOL_PLAIN_STORES
-  *p = v;
-#else
   __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#endif
 }
 constexpr int PR = 64;        // rows per panel block
 constexpr int RS = 256 / PNB;  // rows covered by one pass of the block's 256 loading lanes
 
 constexpr int NSUB = PNB / SB;  // sub-panels per panel
-
-#define CST(k) \
-  do {         \
-  } while (0)
 
 // In-block hand-offs between the waves of one panel block go through LDS words (all waves of a block
 // are resident together). Spins are bounded: a logic error would surface as info = 2 (dx = 0), never
@@ -242,7 +200,6 @@ __device__ __forceinline__ void diag_chain(double (*S)[LP], double (*Lq)[SB][SB 
       Lq[q][lane][SB + 1] = 0.0;
     }
     lds_signal(&flags[q], lane);  // L_qq and L21 (S columns C0..C0+SB) published
-    CST(3 + q);
     if constexpr (REST > 0) {
       // near update: only the next sub-panel's column block (its factorisation waits on it); the far
       // tiles are updated by waves 1/2 (far_update), which also touch column block q+2 -> wait for
@@ -374,7 +331,6 @@ __device__ __forceinline__ void row_chain(double (*S)[LP], double (*X)[LP], cons
 #pragma unroll
       for (int c = 0; c < SB; c++) X[lane][C0 + c] = x[c];
       lds_signal(&flags[NSUB + q], lane);
-      CST(9 + q);
     } else if constexpr (PNB - C0 - SB > 16) {
       if (w <= 2) {  // far S tiles of sub-panel q (column blocks q+2..) while wave 3 solves
         lds_wait_ge(&flags[q], 1, info);
@@ -405,7 +361,6 @@ __device__ __forceinline__ void row_chain(double (*S)[LP], double (*X)[LP], cons
 // active at panel s-1 (i < k0).
 __global__ void __launch_bounds__(256) chol_step_kernel(double* __restrict__ H, int n, int k0, int P1, int P,
                                                         int* __restrict__ info, const int* __restrict__ done) {
-  if (threadIdx.x < 64) CST(0);
   if (*done) return;
   static_assert(UT == 64 && PR == 64 && PNB % 16 == 0 && 256 % PNB == 0, "tiling");
   __shared__ double smem[2 * PNB * LP + 2 * PR * LP + NSUB * SB * (SB + 2) + 3 * NSUB + 1];  // >= 2 * UT * LP (update tiles)
@@ -543,7 +498,6 @@ __global__ void __launch_bounds__(256) chol_step_kernel(double* __restrict__ H, 
     }
   }
   __syncthreads();
-  if (t < 64) CST(1);
   const int w = t >> 6, lane = t & 63, lr = t & 15, lk = (t >> 4) & 3;
   if (upd) {  // look-ahead update of the diagonal block's first column block by panel s-1:
     // A11[:, 0:16] -= L_{s,s-1} L_{s,s-1}[0:16]^T, tile (w, 0) per wave (the rest: la_far_tiles, off the chain)
@@ -551,9 +505,7 @@ __global__ void __launch_bounds__(256) chol_step_kernel(double* __restrict__ H, 
   }
   __syncthreads();  // first column block of the diagonal block complete, flags zeroed
   if (w == 0) {
-    CST(2);
     diag_chain<0>(S, Lq, flags, lane, info);  // the serial chain runs ahead on its own wave
-    CST(7);
   } else {
     if (upd) {  // the diagonal block's other look-ahead tiles (ti, tj), 1 <= tj <= ti: two per wave
       constexpr int CT = PNB / 16;
@@ -566,11 +518,9 @@ __global__ void __launch_bounds__(256) chol_step_kernel(double* __restrict__ H, 
     }
     lds_signal(&flags[5 * NSUB], lane);
     la_rows<0>(X, LR, P1s, flags, w, lane, upd);
-    if (w == 1) CST(8);
     row_chain<0>(S, X, LR, P1s, Lq, flags, w, lane, upd, info);
   }
   __syncthreads();
-  if (w == 0) CST(13);
   {
     constexpr int QX = PR / RS;
 #pragma unroll
@@ -606,38 +556,11 @@ __global__ void __launch_bounds__(256) chol_apply_kernel(const double* __restric
 }
 
 // dx = -x in pose order (0 when the factorisation failed), poses k >= 1 retracted, |dx| early exit
-__global__ void __launch_bounds__(256) dense_finish_kernel(BaArgs a, int K, int n, float delta_thresh) {
+__global__ void __launch_bounds__(256) dense_finish_kernel(BaArgs a, int K, float delta_thresh) {
   if (*a.done) return;
-  const bool failed = *a.info != 0;
-  __shared__ float s_n2[4];
-  float n2 = 0.0f;
-  for (int i = threadIdx.x; i < n; i += blockDim.x) {
-    const int j = i / 7, m = i - 7 * (i / 7);
-    const float d = failed ? 0.0f : (float)(-a.xs[i]);
-    a.dx[a.perm[j] * 7 + m] = d;
-    n2 += d * d;
-  }
-  __syncthreads();
-  for (int k = 1 + threadIdx.x; k < K; k += blockDim.x) {
-    float T[8], xi[7];
-    for (int c = 0; c < 8; c++) T[c] = a.Twc[k * 8 + c];
-    for (int c = 0; c < 7; c++) xi[c] = a.dx[(k - 1) * 7 + c];
-    m3s::retrSim3_d(xi, T);  // fp64 retraction (m3s_common.hpp)
-    for (int c = 0; c < 8; c++) a.Twc[k * 8 + c] = T[c];
-  }
-  n2 = wave_sum(n2);
-  if ((threadIdx.x & 63) == 0) s_n2[threadIdx.x >> 6] = n2;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const float nrm = sqrtf(s_n2[0] + s_n2[1] + s_n2[2] + s_n2[3]);
-    *a.iters += 1;
-    if (nrm < delta_thresh) *a.done = 1;
-    if (*a.info == 2) {  // an LDS hand-off stalled (lds_wait_ge): sticky, the loop ends, the host reports M3S_ESTALL
-      *a.stalled = 1;
-      *a.done = 1;
-    }
-    *a.info = 0;
-  }
+  const int info = *a.info;  // 1: a non-positive pivot; 2: an LDS hand-off stalled (lds_wait_ge)
+  m3s::ba_finish_step<7>(a, a.xs, K, delta_thresh, info != 0, info == 2);
+  if (threadIdx.x == 0) *a.info = 0;
 }
 
 }  // namespace m3s_dense
@@ -663,6 +586,6 @@ extern "C" hipError_t m3s_launch_ba_solve_dense(const BaArgs* a, int K, int nL, 
     }
     hipLaunchKernelGGL(m3s_dense::chol_apply_kernel, dim3((n + 3) / 4), dim3(256), 0, s, a->H, a->xs, n, a->done);
   }
-  hipLaunchKernelGGL(m3s_dense::dense_finish_kernel, dim3(1), dim3(256), 0, s, *a, K, n, delta_thresh);
+  hipLaunchKernelGGL(m3s_dense::dense_finish_kernel, dim3(1), dim3(256), 0, s, *a, K, delta_thresh);
   return hipGetLastError();
 }

@@ -4,7 +4,7 @@
 // (/root/reference/mast3r_slam/backend/src/gn_kernels.cu:57-159), re-analysing the pattern on every GN
 // iteration. Here the pattern is analysed ONCE per plan, at 7x7-block granularity (one block per
 // keyframe pose), and the numeric factorisation of every GN iteration runs on the device
-// (ba_sparse_factor_kernel, ba.hip):
+// (ba_sparse_factor_kernel, ba_sparse.hip):
 //   * ordering: minimum degree on the keyframe graph (ties to the lowest index), which keeps the fill of
 //     the long chain + loop-closure graphs of SLAM small (K = 256 chess graph: 1922 factor blocks
 //     instead of 32640 dense, elimination tree height 68 instead of 255);

@@ -1,6 +1,7 @@
-// Internal (non-ABI) structs, constants and launchers shared by ba.hip, ba_dense.hip and abi_ba.cpp. The public C ABI
-// is include/m3s.h.
+// Internal (non-ABI) structs, constants and launchers shared by ba.hip, ba_sparse.hip, ba_dense.hip and abi_ba.cpp.
+// The public C ABI is include/m3s.h.
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
 #include <hip/hip_runtime.h>
 
@@ -10,11 +11,18 @@
 #define BA_MODE_CALIB_RAW 3  // calib residuals on points NOT constrained to their pixel rays (m3s.h M3S_BA_MODE_CALIB_RAW)
 
 #ifndef M3S_BA_SP_WAVES
-#define M3S_BA_SP_WAVES 16  // waves of the one-workgroup sparse factorisation (ba.hip) and of its cost model (abi_ba.cpp)
+#define M3S_BA_SP_WAVES 16  // waves of the one-workgroup sparse factorisation (ba_sparse.hip) and of its cost model (abi_ba.cpp)
 #endif
 namespace m3s {
 constexpr int SP_PLAN_BYTES = 144 * 1024;  // LDS of the one-workgroup factor kernel: the plan's loop tables and x
+// What that kernel keeps in LDS for a plan: the loop tables (plan_bytes: col_ptr .. sidx and, with flow, the dataflow
+// schedule; padded to 16 B), x (8 doubles per column) and, for the dataflow schedule, 3 flag words per column. A plan
+// that needs more than SP_PLAN_BYTES runs the global-table instance, level-synchronously: the host (build_symbolic)
+// drops its schedule by this rule and the launcher (m3s_launch_ba_solve) picks the instance by it.
+inline size_t ba_sp_lds_bytes(size_t plan_bytes, int nb, bool flow) {
+  return ((plan_bytes + 15) & ~(size_t)15) + (size_t)nb * 64 + (flow ? (size_t)nb * 12 : 0);
 }
+}  // namespace m3s
 
 struct BaParams {
   int mode;

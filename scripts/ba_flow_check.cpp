@@ -1,5 +1,5 @@
 // Host check of the BA dataflow schedule (ba_pattern.cpp ba_flow_schedule) against the device protocol of
-// ba_sparse_factor_kernel's flow path (ba.hip): interprets every wave's task list with the kernel's wait
+// ba_sparse_factor_kernel's flow path (ba_sparse.hip): interprets every wave's task list with the kernel's wait
 // conditions (update groups landed per column, source columns factored, x of struct(j) done) one task at a time,
 // and fails on a deadlock (no wave can proceed), on an update group applied out of step order, on a factor task
 // before all of its column's groups, or on a column left unfinished. Prints the schedule's simulated makespan.

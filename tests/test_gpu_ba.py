@@ -404,6 +404,42 @@ def test_factor_schedule_stall_raises_not_silent(monkeypatch):
     assert sh.iterations() == 1 and not torch.equal(T1, G["Twc0"].to(dev))
 
 
+@pytest.mark.parametrize("n_kf", [48, 97])
+def test_sparse_solve_schedules_are_bit_identical(n_kf, monkeypatch):
+    """Every schedule of the block-sparse solve (ba_sparse.hip) runs the same per-task arithmetic in the same order:
+    poses and dx after two GN iterations are bit-identical across M3S_BA_FLOW in {1, 0} (dataflow flags / a barrier
+    per level) crossed with M3S_BA_WIDE in {unset, 0, 1000000} (the launch-cost split / every step a
+    ba_sparse_step_kernel launch / every step inside the one-workgroup kernel). 48 keyframes (47 columns, 500 factor
+    blocks, 26 levels, ~33 KB of loop tables): the LDS instance of ba_sparse_factor_kernel, with the dataflow schedule
+    and columns of more than 128 rows. 97 keyframes (96 columns, 1612 blocks, 49 levels, ~160 KB of tables, over the
+    144 KB the kernel keeps in LDS): the global-table instance and its level-synchronous back substitution."""
+    from m3s.config import config
+    from m3s.dist_ba import gauss_newton_sharded
+    from m3s.synthetic import make_graph, two_way
+
+    monkeypatch.setenv("M3S_BA_SOLVER", "sparse")
+    G = make_graph(n_kf=n_kf, H=12, W=16, seed=3)
+    ii, jj, idx, valid, Q = two_way(G)
+    d = lambda t: t.cuda().contiguous()
+    args = (d(G["Xs"]), d(G["Cs"][..., 0]), d(ii), d(jj), d(idx), d(valid[..., 0]), d(Q[..., 0]), config["local_opt"],
+            2, 0.0)
+    out = {}
+    for flow in ("1", "0"):
+        for wide in (None, "0", "1000000"):
+            monkeypatch.setenv("M3S_BA_FLOW", flow)
+            if wide is None:
+                monkeypatch.delenv("M3S_BA_WIDE", raising=False)
+            else:
+                monkeypatch.setenv("M3S_BA_WIDE", wide)
+            T = d(G["Twc0"])
+            dx = gauss_newton_sharded("rays", T, *args)[0]
+            out[flow, wide] = (T.cpu().numpy(), dx.cpu().numpy())
+    T0, dx0 = out["1", None]
+    assert np.isfinite(T0).all() and np.abs(dx0).max() > 0 and not np.array_equal(T0, G["Twc0"].numpy())
+    for key, (T, dx) in out.items():
+        assert np.array_equal(T, T0) and np.array_equal(dx, dx0), key
+
+
 @pytest.mark.parametrize("mode", ["points", "rays", "calib"])
 def test_pack_fused_into_first_linearisation_is_bit_identical(mode, monkeypatch):
     """A call that packs every edge builds the point records inside its first linearisation (ba_lin_kernel<PACK>,
