@@ -159,18 +159,12 @@ __device__ __forceinline__ void lm_iter(LmState& m, const float* __restrict__ im
   }
 }
 
-struct LmNoHook {
-  __device__ __forceinline__ void operator()(int) const {}
-};
-
 // OCC: X11b non-null, xo gets X11 at the final (.long()) pixel, gathered during the last iteration (lm_iter<true>).
-// after_iter(i) runs behind iteration i of the max_iter - 1 iterations in front of the last one (the fused refine
-// kernel issues loads of its own there; it must be wave-uniform and touch no LM state)
-template <bool OCC, class Hook = LmNoHook>
+template <bool OCC>
 __device__ __forceinline__ void iter_proj_point(const float* __restrict__ img, int H, int W, const float p[3],
                                                 float& u, float& v, bool& conv, int max_iter, float lambda_init,
                                                 float cost_thresh, const float* __restrict__ X11b = nullptr,
-                                                float* xo = nullptr, Hook after_iter = Hook()) {
+                                                float* xo = nullptr) {
   LmState m;
   m.u = fminf(fmaxf(u, 1.0f), (float)(W - 2));
   m.v = fminf(fmaxf(v, 1.0f), (float)(H - 2));
@@ -200,10 +194,7 @@ __device__ __forceinline__ void iter_proj_point(const float* __restrict__ img, i
   m.e2 = m.s[2] * r_norm_inv - p[2];
   m.cost = m.e0 * m.e0 + m.e1 * m.e1 + m.e2 * m.e2;
   if constexpr (OCC) {
-    for (int i = 0; i < max_iter - 1; i++) {
-      lm_iter<false>(m, img, H, W, p, cost_thresh, nullptr, nullptr);
-      after_iter(i);
-    }
+    for (int i = 0; i < max_iter - 1; i++) lm_iter<false>(m, img, H, W, p, cost_thresh, nullptr, nullptr);
     if (max_iter > 0) lm_iter<true>(m, img, H, W, p, cost_thresh, X11b, xo);
   } else {
     for (int i = 0; i < max_iter; i++) lm_iter<false>(m, img, H, W, p, cost_thresh, nullptr, nullptr);

@@ -30,7 +30,7 @@
 //   * On the fused match path the same launch first runs the projection search for the tile's pixels (FUSE_PROJ,
 //     m3s_proj.hpp): no launch and no p1 round trip between the LM search and the levels.
 //   * Every block of a 512x512 launch is resident at once, so the waves' issue priority follows their progress
-//     (RT_PRIO_TABLE below: a wave a level behind the others on its SIMD outranks them) and the blocks finish together.
+//     (rt_prio below: a wave a level behind the others on its SIMD outranks them) and the blocks finish together.
 // Compiled with -ffp-contract=off and -fno-slp-vectorize: each candidate's half sum stays a scalar chain (VOP2
 // v_add_f16 for the even channel, SDWA v_add_f16 for the odd one) instead of the SLP vectoriser pairing two
 // candidates per v_pk_add_f16 behind v_perm / v_pack transposes. Measured issue costs on gfx950 at 4 waves/SIMD
@@ -41,41 +41,20 @@
 
 namespace m3s {
 
-// Tile geometry (RT_WAVES waves per block, two pixel rows per wave). The shipped build: 32 x 8 tiles, 4 waves, a
-// 40-row window (40 KiB, four blocks per CU). RT_TALL (experiment): 32 x 16 tiles, 8 waves, a 56-row window (56 KiB,
-// two blocks per CU: the same 16 waves per CU), so the +-3d halo of a level's window is shared by twice the pixels.
-#ifndef RT_TALL
-#define RT_TALL 0
-#endif
-#define RT_TW 32
-#define RT_COLS 64
-#define RT_PCOLS 48
-#if RT_TALL
-#define RT_WAVES 8
-#define RT_TH 16
-#define RT_ROWS 56
-#define RT_PROWS 24
-#define RT_DROWS 36
-#else
-#define RT_WAVES 4
-#define RT_TH 8
-#define RT_ROWS 40  // 40 x 64 x 16 B = 40 KiB per block: four blocks per CU
+// Tile geometry: 32 x 8 pixel tiles, RT_WAVES waves per block, two pixel rows per wave
+constexpr int RT_TW = 32, RT_TH = 8, RT_WAVES = 4, RT_THREADS = 64 * RT_WAVES;
+constexpr int RT_MIN_BLOCKS = 16 / RT_WAVES;  // blocks per CU the register budget is sized for (16 waves: 128 VGPRs)
+constexpr int RT_ROWS = 40, RT_COLS = 64;  // 40 x 64 x 16 B = 40 KiB per block: four blocks per CU (the LDS limit too)
 // packed window (SCREEN, d = 1): all three chunk planes resident at once, 3 x 17 rows x 48 columns x 16 B = 38.25 KiB
 // (the d = 1 cover is 16 x 39-40 on 97 % of the synthetic 512x512 tiles, scripts/refine_window_stats.py)
-#define RT_PROWS 17
+constexpr int RT_PROWS = 17, RT_PCOLS = 48, RT_PPLANE = RT_PROWS * RT_PCOLS;
 // double-buffered window (SCREEN, d = 2): two 26-row x 48-column chunk buffers (2 x 19.5 KiB), chunk c + 1 streams in
 // while chunk c is screened (the d = 2 cover is 23 x 45-47 on 97.6 % of the synthetic 512x512 tiles)
-#define RT_DROWS 26
-#endif
+constexpr int RT_DROWS = 26, RT_DBUF = RT_DROWS * RT_PCOLS;
 static_assert(RT_TH == 2 * RT_WAVES, "two pixel rows per wave");
 static_assert(3 * RT_PROWS * RT_PCOLS <= RT_ROWS * RT_COLS && 2 * RT_DROWS * RT_PCOLS <= RT_ROWS * RT_COLS,
               "the packed and double-buffered windows share the block's window");
-#define RT_THREADS (64 * RT_WAVES)
-#define RT_PPLANE (RT_PROWS * RT_PCOLS)
-#define RT_DBUF (RT_DROWS * RT_PCOLS)
-#ifndef RT_INPLACE_MAX  // window outliers a wave scores in place at one level (more: deferred to the list)
-#define RT_INPLACE_MAX 8
-#endif
+constexpr int RT_INPLACE_MAX = 8;  // window outliers a wave scores in place at one level (more: deferred to the list)
 
 typedef __attribute__((address_space(1))) const void* gvoid_t;
 typedef __attribute__((address_space(3))) void* lvoid_t;
@@ -83,7 +62,7 @@ typedef __attribute__((address_space(3))) void* lvoid_t;
 // Wave issue priority (s_setprio, user priority 0..3: the SIMD's arbiter takes the highest priority first, then the
 // oldest wave). All 1024 blocks of a 512x512 launch are resident from the first microsecond, four per CU, so under
 // oldest-first alone the blocks dispatched last lose every issue conflict and the launch ends on them (block 75 us at
-// the median, launch 105 us). Two uses, both compile-time (RT_PRIO_TABLE; DESIGN section 4 refine has the measurements):
+// the median, launch 105 us). Two uses, both compile-time (DESIGN section 4 refine has the measurements):
 //   * by phase: a block's chain alternates short issue phases that each start a long latency (the ~10 DMA rows of a
 //     fill, a survivor trip's six loads, the LM gathers, the level-start exchange three other waves wait for) with long
 //     dot2 bursts that start none. LM: the FUSE_PROJ instance's projection search and the D21 row loads behind it;
@@ -92,31 +71,11 @@ typedef __attribute__((address_space(3))) void* lvoid_t;
 //     screen_chunk / score_chunk, the mask and the exact chains.
 //   * by level (LAG, "laggards first"): every value falls by one per level below d = 3, so a wave that is a level
 //     behind the others on its SIMD outranks them in every phase and the blocks finish together.
-// The shipped table 3 does both; by level alone (4) measured the same median with more spread, by phase alone (1, 2)
-// a quarter of the gain. The kernel has no spin-wait, so priorities change neither results nor liveness. An all-zero
-// table emits no s_setprio at all.
-#ifndef RT_PRIO_TABLE
-#define RT_PRIO_TABLE 3
-#endif
-// columns: LM, START, FILL, SURV, SCORE, LAG
-#if RT_PRIO_TABLE == 0  // none: oldest-first
-#define RT_PRIO_ROW 0, 0, 0, 0, 0, 0
-#elif RT_PRIO_TABLE == 1  // the latency-starting phases over the bursts
-#define RT_PRIO_ROW 3, 3, 3, 3, 0, 0
-#elif RT_PRIO_TABLE == 2  // the same, the LM phase left at the default
-#define RT_PRIO_ROW 0, 3, 3, 3, 0, 0
-#elif RT_PRIO_TABLE == 3  // laggards first: 3 / 2 (latency phases / bursts) at d >= 3, 2 / 1 at d = 2, 1 / 0 at d = 1
-#define RT_PRIO_ROW 3, 3, 3, 3, 2, 1
-#elif RT_PRIO_TABLE == 4  // laggards first by level alone: 3 at d >= 3, 2 at d = 2, 1 at d = 1
-#define RT_PRIO_ROW 3, 3, 3, 3, 3, 1
-#else
-#error "RT_PRIO_TABLE: 0..4"
-#endif
-constexpr int RT_PRIO_TAB[6] = {RT_PRIO_ROW};
-constexpr int RT_PRIO_LM = RT_PRIO_TAB[0], RT_PRIO_START = RT_PRIO_TAB[1], RT_PRIO_FILL = RT_PRIO_TAB[2],
-              RT_PRIO_SURV = RT_PRIO_TAB[3], RT_PRIO_SCORE = RT_PRIO_TAB[4], RT_PRIO_LAG = RT_PRIO_TAB[5];
-constexpr bool RT_PRIO_ON =
-    (RT_PRIO_LM | RT_PRIO_START | RT_PRIO_FILL | RT_PRIO_SURV | RT_PRIO_SCORE | RT_PRIO_LAG) != 0;
+// Doing both measured best: by level alone the same median with more spread, by phase alone a quarter of the gain
+// (profiles/refine_prio_ab.json). The kernel has no spin-wait, so priorities change neither results nor liveness.
+// Laggards first: 3 / 2 (latency phases / bursts) at d >= 3, 2 / 1 at d = 2, 1 / 0 at d = 1.
+constexpr int RT_PRIO_LM = 3, RT_PRIO_START = 3, RT_PRIO_FILL = 3, RT_PRIO_SURV = 3, RT_PRIO_SCORE = 2,
+              RT_PRIO_LAG = 1;
 // the priority of phase value p at level d (d = 0: outside the levels)
 constexpr int rt_prio_at(int p, int d) {
   const int q = (RT_PRIO_LAG && d > 0 && d < 3) ? p - (3 - d) : p;
@@ -124,24 +83,85 @@ constexpr int rt_prio_at(int p, int d) {
 }
 template <int P, int D = 0>
 __device__ __forceinline__ void rt_prio() {
-  if constexpr (RT_PRIO_ON) __builtin_amdgcn_s_setprio(rt_prio_at(P, D));
+  __builtin_amdgcn_s_setprio(rt_prio_at(P, D));
 }
 // ... where the wave is known to run at phase value FROM: nothing to do when the two are equal
 template <int FROM, int P, int D>
 __device__ __forceinline__ void rt_prio_from() {
-  if constexpr (RT_PRIO_ON && rt_prio_at(FROM, D) != rt_prio_at(P, D)) __builtin_amdgcn_s_setprio(rt_prio_at(P, D));
+  if constexpr (rt_prio_at(FROM, D) != rt_prio_at(P, D)) __builtin_amdgcn_s_setprio(rt_prio_at(P, D));
 }
 
-#ifdef M3S_REFINE_STATS  // (experiment builds only) per-level deferred lanes / waves
+// Measurement builds. Each is a pair of helpers that compile to nothing without its macro.
+// M3S_REFINE_STATS (the counts quoted in DESIGN section 4; m3s_debug_refine_stats reads them): per level d, deferred
+// lanes [2d] and waves [2d + 1]; survivors, the lanes' sum [32 + 2d] and the per-wave maximum summed [33 + 2d].
+#ifdef M3S_REFINE_STATS
 __device__ unsigned long long g_refine_stats[64];
 #endif
-#ifdef M3S_REFINE_BSTAMPS  // (experiment builds only) per-block start / end s_memrealtime, hardware id, active lanes
+template <int D>
+__device__ __forceinline__ void stats_outliers(int lane, uint64_t om) {
+#ifdef M3S_REFINE_STATS
+  if (lane == 0 && om) {
+    atomicAdd(&g_refine_stats[2 * D], (unsigned long long)__popcll(om));
+    atomicAdd(&g_refine_stats[2 * D + 1], 1ull);
+  }
+#endif
+}
+template <int D>
+__device__ __forceinline__ void stats_survivors(int lane, uint64_t m) {
+#ifdef M3S_REFINE_STATS
+  int mx = __popcll(m), sm = mx;
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    mx = max(mx, __shfl_xor(mx, off, 64));
+    sm += __shfl_xor(sm, off, 64);
+  }
+  if (lane == __ffsll((long long)__ballot(1)) - 1) {
+    atomicAdd(&g_refine_stats[32 + 2 * D], (unsigned long long)sm);
+    atomicAdd(&g_refine_stats[33 + 2 * D], (unsigned long long)mx);
+  }
+#endif
+}
+// M3S_REFINE_BSTAMPS (scripts/refine_blocks.py, scripts/refine_fuse_stamps.py): per block four words, [0] the levels'
+// start (FUSE_PROJ: the kernel's first instruction), [1] the block's end, [2] its hardware id, [3] its active lanes
+// (FUSE_PROJ: when the LM phase ended); s_memrealtime ticks.
+#ifdef M3S_REFINE_BSTAMPS
 __device__ unsigned long long g_refine_bstamps[8192 * 4];
 #endif
+__device__ __forceinline__ unsigned long long bstamp_clock() {
+#ifdef M3S_REFINE_BSTAMPS
+  return __builtin_amdgcn_s_memrealtime();
+#else
+  return 0ull;
+#endif
+}
+__device__ __forceinline__ void bstamp_levels_start(bool fuse_proj, unsigned long long stamp_top) {
+#ifdef M3S_REFINE_BSTAMPS
+  if (threadIdx.x == 0 && blockIdx.x < 8192)
+    g_refine_bstamps[blockIdx.x * 4 + 0] = fuse_proj ? stamp_top : __builtin_amdgcn_s_memrealtime();
+#endif
+}
+__device__ __forceinline__ void bstamp_block_end(bool fuse_proj, unsigned long long stamp_lm, bool active,
+                                                 uint4* lds) {
+#ifdef M3S_REFINE_BSTAMPS
+  const unsigned long long nact = __popcll(__ballot(active));
+  // aliases the window (done with): a separate __shared__ array would push the block past 40 KiB of LDS and
+  // change the occupancy being measured (4 -> 3 blocks per CU)
+  unsigned long long* s_act = reinterpret_cast<unsigned long long*>(&lds[0]);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) s_act[threadIdx.x >> 6] = nact;
+  __syncthreads();
+  if (threadIdx.x == 0 && blockIdx.x < 8192) {
+    unsigned hw;
+    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
+    g_refine_bstamps[blockIdx.x * 4 + 1] = __builtin_amdgcn_s_memrealtime();
+    g_refine_bstamps[blockIdx.x * 4 + 2] = hw;
+    unsigned long long na = 0;
+    for (int w = 0; w < RT_WAVES; w++) na += s_act[w];
+    g_refine_bstamps[blockIdx.x * 4 + 3] = fuse_proj ? stamp_lm : na;
+  }
+#endif
+}
 
-// One level of one pixel by the whole wave (cu, cv, max_score, sq wave-uniform): lane c < 49 scores
-// candidate (c / 7, c % 7) from global memory; the first candidate in scan order holding the wave
-// maximum wins if it beats the running max — the sequential strict-'>' scan's result.
 // D11h layouts: PLANAR (fused path, written by prep_rays_kernel) = per image three chunk planes (H,W,8) f16, so a
 // window row of one chunk is one contiguous 16 B-per-pixel run; otherwise the caller's (H,W,24) f16.
 template <bool PLANAR>
@@ -156,6 +176,26 @@ __device__ __forceinline__ void load_chunks(const h1* p, size_t N, uint4& c0, ui
   c2 = *reinterpret_cast<const uint4*>(p + 2 * cs);
 }
 
+// The exact score of one candidate: the c10::Half chain, from +0 sequentially over channels 0..23 (c0, c1, c2: the
+// candidate's three 8-channel chunks)
+__device__ __forceinline__ h1 exact_score(const h2* q, uint4 c0, uint4 c1, uint4 c2) {
+  h1 sc = (h1)0.0f;
+  add8(sc, &q[0], c0);
+  add8(sc, &q[4], c1);
+  add8(sc, &q[8], c2);
+  return sc;
+}
+// ... and the scan's step for it: strict '>' against the running max
+__device__ __forceinline__ void take_if_greater(h1 sc, int c, h1& max_score, int& bi) {
+  if (sc > max_score) {
+    max_score = sc;
+    bi = c;
+  }
+}
+
+// One level of one pixel by the whole wave (cu, cv, max_score, sq wave-uniform): lane c < 49 scores
+// candidate (c / 7, c % 7) from global memory; the first candidate in scan order holding the wave
+// maximum wins if it beats the running max — the sequential strict-'>' scan's result.
 template <int D, bool PLANAR>
 __device__ __forceinline__ void wave_level(const h1* __restrict__ img, int H, int W, const h2* sq, int& cu, int& cv,
                                            h1& max_score, int lane) {
@@ -166,10 +206,7 @@ __device__ __forceinline__ void wave_level(const h1* __restrict__ img, int H, in
   uint4 c0, c1, c2;
   load_chunks<PLANAR>(pix_ptr<PLANAR>(img, (size_t)min(max(v, 0), H - 1) * W + min(max(u, 0), W - 1)),
                       (size_t)H * W, c0, c1, c2);
-  h1 sc = (h1)0.0f;
-  add8(sc, &sq[0], c0);
-  add8(sc, &sq[4], c1);
-  add8(sc, &sq[8], c2);
+  const h1 sc = exact_score(sq, c0, c1, c2);
   const float sf = (ok && sc == sc) ? (float)sc : -INFINITY;  // NaN never wins a strict '>'
   float vmax = sf;
 #pragma unroll
@@ -223,24 +260,17 @@ __device__ __forceinline__ void screen_chunk(const uint4* base, const h2* q4, fl
   constexpr int G = 7;
 #pragma unroll
   for (int i = 0; i < G; i++) {
-    // the column's candidate reads in flight together (RT_COLBATCH of them: one LDS latency per batch, not per
-    // candidate)
-#ifndef RT_COLBATCH
-#define RT_COLBATCH 7
-#endif
+    // the column's candidate reads in flight together (one LDS latency per column, not per candidate)
+    uint4 c[G];
 #pragma unroll
-    for (int j0 = 0; j0 < G; j0 += RT_COLBATCH) {
-      uint4 c[RT_COLBATCH];
+    for (int j = 0; j < G; j++) c[j] = base[j * D * STRIDE + i * D];
 #pragma unroll
-      for (int j = j0; j < min(G, j0 + RT_COLBATCH); j++) c[j - j0] = base[j * D * STRIDE + i * D];
+    for (int j = 0; j < G; j++) {
+      const h2* cv = reinterpret_cast<const h2*>(&c[j]);
+      float t = seed ? 0.0f : a[i * G + j];
 #pragma unroll
-      for (int j = j0; j < min(G, j0 + RT_COLBATCH); j++) {
-        const h2* cv = reinterpret_cast<const h2*>(&c[j - j0]);
-        float t = seed ? 0.0f : a[i * G + j];
-#pragma unroll
-        for (int k = 0; k < 4; k++) t = __builtin_amdgcn_fdot2(q4[k], cv[k], t, false);
-        a[i * G + j] = t;
-      }
+      for (int k = 0; k < 4; k++) t = __builtin_amdgcn_fdot2(q4[k], cv[k], t, false);
+      a[i * G + j] = t;
     }
     // pin the column's dot products here: otherwise the last chunk's are sunk into the survivor code and all 49
     // candidate loads stay live across it (1000+ spilled VGPRs)
@@ -280,43 +310,26 @@ template <int D, bool PLANAR>
 __device__ __forceinline__ void exact_survivors(const h1* __restrict__ img, int H, int W, const h2* q, int u_lo,
                                                 int v_lo, uint64_t m, h1& max_score, int& bi) {
   while (__ballot(m != 0)) {  // wave-uniform trip count: the lane with the most survivors
-    const int ca = m != 0 ? __ffsll((long long)m) - 1 : -1;
-    m &= m - 1;
-    const int cb = m != 0 ? __ffsll((long long)m) - 1 : -1;
-    m &= m - 1;
-    uint4 a0, a1, a2, b0, b1, b2;
-    rt_prio_from<RT_PRIO_SCORE, RT_PRIO_SURV, D>();  // the trip's loads start an L2 round trip
-    if (ca >= 0) {
-      const int i = ca / 7, j = ca - 7 * i;
-      load_chunks<PLANAR>(pix_ptr<PLANAR>(img, (size_t)(v_lo + j * D) * W + (u_lo + i * D)), (size_t)H * W, a0, a1,
-                          a2);
+    int c[2];
+    uint4 x[2][3];
+#pragma unroll
+    for (int k = 0; k < 2; k++) {
+      c[k] = m != 0 ? __ffsll((long long)m) - 1 : -1;
+      m &= m - 1;
     }
-    if (cb >= 0) {
-      const int i = cb / 7, j = cb - 7 * i;
-      load_chunks<PLANAR>(pix_ptr<PLANAR>(img, (size_t)(v_lo + j * D) * W + (u_lo + i * D)), (size_t)H * W, b0, b1,
-                          b2);
+    rt_prio_from<RT_PRIO_SCORE, RT_PRIO_SURV, D>();  // the trip's loads start an L2 round trip
+#pragma unroll
+    for (int k = 0; k < 2; k++) {
+      if (c[k] >= 0) {
+        const int i = c[k] / 7, j = c[k] - 7 * i;
+        load_chunks<PLANAR>(pix_ptr<PLANAR>(img, (size_t)(v_lo + j * D) * W + (u_lo + i * D)), (size_t)H * W, x[k][0],
+                            x[k][1], x[k][2]);
+      }
     }
     rt_prio_from<RT_PRIO_SURV, RT_PRIO_SCORE, D>();
-    if (ca >= 0) {
-      h1 sc = (h1)0.0f;
-      add8(sc, &q[0], a0);
-      add8(sc, &q[4], a1);
-      add8(sc, &q[8], a2);
-      if (sc > max_score) {
-        max_score = sc;
-        bi = ca;
-      }
-    }
-    if (cb >= 0) {
-      h1 sc = (h1)0.0f;
-      add8(sc, &q[0], b0);
-      add8(sc, &q[4], b1);
-      add8(sc, &q[8], b2);
-      if (sc > max_score) {
-        max_score = sc;
-        bi = cb;
-      }
-    }
+#pragma unroll
+    for (int k = 0; k < 2; k++)
+      if (c[k] >= 0) take_if_greater(exact_score(q, x[k][0], x[k][1], x[k][2]), c[k], max_score, bi);
   }
 }
 
@@ -342,15 +355,7 @@ __device__ __forceinline__ void exact_survivors_lds(const uint4* base, const h2*
     m &= m - 1;
     const int i = c / 7, j = c - 7 * i;
     const uint4* p = base + j * D * RT_PCOLS + i * D;
-    const uint4 c0 = p[0], c1 = p[RT_PPLANE], c2 = p[2 * RT_PPLANE];
-    h1 sc = (h1)0.0f;
-    add8(sc, &q[0], c0);
-    add8(sc, &q[4], c1);
-    add8(sc, &q[8], c2);
-    if (sc > max_score) {
-      max_score = sc;
-      bi = c;
-    }
+    take_if_greater(exact_score(q, p[0], p[RT_PPLANE], p[2 * RT_PPLANE]), c, max_score, bi);
   }
 }
 
@@ -362,17 +367,58 @@ struct TileCtx {
   int bn;       // batch * N + pixel
   int4* olist;  // deferred-pixel list (nullable: score outliers in place)
   int* ocount;
-  unsigned lds_addr;  // LDS byte address of the window (the block's __shared__ array)
-  float bq;      // SCREEN: this lane's bound B (0.0125 |q| cmax + 2^-18)
-  bool sok;      // SCREEN: the bound is usable (|q| cmax <= 16384 and finite)
+  float bq = 0.0f;   // SCREEN: this lane's bound B (0.0125 |q| cmax + 2^-18)
+  bool sok = false;  // SCREEN: the bound is usable (|q| cmax <= 16384 and finite)
 };
 
+// One level's window over D11 (block-uniform) and this lane's column of it
+struct LevelWin {
+  int wx0, wy0;       // image coordinates of the window's corner
+  int nrows, ncols;   // rows and columns actually filled
+  bool packed, dbuf;  // layout: the packed (d = 1) or the double-buffered (d = 2) window, else the general one
+  bool col_in;        // this lane's column is filled
+  int lane_off;       // ... and its offset in a D11h row, in halves
+};
+
+// This lane's 7x7 candidate grid at one level
+struct LaneGrid {
+  int u_lo, v_lo;  // image coordinates of candidate (0, 0)
+  int bx, by;      // ... and its window coordinates
+  bool in;         // the lane is active and all 49 candidates lie in the filled window
+};
+// re-centre on the level's winner bi (scan index; -1: none beat the running max)
+template <int D>
+__device__ __forceinline__ void recentre(const LaneGrid& g, int bi, int& cu, int& cv) {
+  if (bi >= 0) {
+    cu = g.u_lo + (bi / 7) * D;
+    cv = g.v_lo + (bi % 7) * D;
+  }
+}
+
+// Rows y0, y0 + RT_WAVES, .. < w.nrows of one 8-channel chunk plane into LDS, dst + y * stride (uint4 units): one DMA
+// (64 lanes x 16 B) per window row, only the cover's columns. The row base (and the chunk plane) is wave-uniform
+// (scalar), the column offset per lane. ASM_DMA: lds_dma_row instead of the builtin (the double-buffered window).
+template <bool PLANAR, bool ASM_DMA>
+__device__ __forceinline__ void fill_rows(const TileCtx& t, const LevelWin& w, uint4* dst, int stride, int chunk,
+                                          int y0) {
+  const size_t cstride = PLANAR ? (size_t)t.H * t.W * 8 : 8, rstride = (size_t)t.W * (PLANAR ? 8 : 24);
+  for (int y = y0; y < w.nrows; y += RT_WAVES) {
+    const int gy = min(max(w.wy0 + y, 0), t.H - 1);
+    const h1* rowp = t.img + (size_t)gy * rstride + chunk * cstride;
+    if (w.col_in) {
+      if constexpr (ASM_DMA)
+        lds_dma_row(rowp + w.lane_off, (unsigned)(uintptr_t)(lvoid_t)&dst[y * stride]);
+      else
+        __builtin_amdgcn_global_load_lds((gvoid_t)(rowp + w.lane_off), (lvoid_t)&dst[y * stride], 16, 0, 0);
+    }
+  }
+}
+
+// The level's window: the bbox of the inlier centres, exchanged across the block's waves, and its placement
 template <int D, bool SCREEN, bool PLANAR>
-__device__ __forceinline__ void refine_level(const TileCtx& t, bool& active, const h2* q, int& cu, int& cv,
-                                             h1& max_score, uint4* lds, int (*s_red)[4], bool first) {
-  constexpr int R = 3, G = 2 * R + 1, F = 24, RD = R * D;
-  const int lane = t.lane, wid = t.wid, H = t.H, W = t.W;
-  rt_prio<RT_PRIO_START, D>();  // three other waves wait at the exchange's barriers
+__device__ __forceinline__ LevelWin level_window(const TileCtx& t, bool active, int cu, int cv, int (*s_red)[4]) {
+  constexpr int RD = 3 * D;
+  const int lane = t.lane, wid = t.wid;
   // bbox of the inlier centres (within 16 px of pixel + the tile's flow estimate t.fu/t.fv)
   const bool inl = active && abs(cu - t.u_pix - t.fu) <= 16 && abs(cv - t.v_pix - t.fv) <= 16;
   int mnu = inl ? cu : INT_MAX, mxu = inl ? cu : INT_MIN;
@@ -412,28 +458,32 @@ __device__ __forceinline__ void refine_level(const TileCtx& t, bool& active, con
   // bbox middle deferred the cluster itself (d = 4 on the synthetic 512x512 pair: 1502 deferred lanes against 54,
   // scripts/refine_window_stats.py)
   const int x_lo = mnu - RD, x_hi = mxu + RD, y_lo = mnv - RD, y_hi = mxv + RD;
-  bool packed = false, dbuf = false;  // block-uniform: every input is
-  if constexpr (SCREEN && D == 1) packed = x_hi - x_lo + 1 <= RT_PCOLS && y_hi - y_lo + 1 <= RT_PROWS;
-  if constexpr (SCREEN && D == 2) dbuf = x_hi - x_lo + 1 <= RT_PCOLS && y_hi - y_lo + 1 <= RT_DROWS;
-  const int wc = (packed || dbuf) ? RT_PCOLS : RT_COLS, wr = packed ? RT_PROWS : (dbuf ? RT_DROWS : RT_ROWS);
-  const int wx0 = (x_hi - x_lo + 1 <= wc) ? x_lo : t.tcu - wc / 2;
-  const int wy0 = (y_hi - y_lo + 1 <= wr) ? y_lo : t.tcv - wr / 2;
+  LevelWin w;
+  w.packed = w.dbuf = false;  // block-uniform: every input is
+  if constexpr (SCREEN && D == 1) w.packed = x_hi - x_lo + 1 <= RT_PCOLS && y_hi - y_lo + 1 <= RT_PROWS;
+  if constexpr (SCREEN && D == 2) w.dbuf = x_hi - x_lo + 1 <= RT_PCOLS && y_hi - y_lo + 1 <= RT_DROWS;
+  const int wc = (w.packed || w.dbuf) ? RT_PCOLS : RT_COLS;
+  const int wr = w.packed ? RT_PROWS : (w.dbuf ? RT_DROWS : RT_ROWS);
+  w.wx0 = (x_hi - x_lo + 1 <= wc) ? x_lo : t.tcu - wc / 2;
+  w.wy0 = (y_hi - y_lo + 1 <= wr) ? y_lo : t.tcv - wr / 2;
   // rows and columns actually filled: the bbox cover, clipped to the window (a fine level's cover is ~40 of the 64
   // columns: the fill, bound by L2 -> LDS bandwidth, moves only those)
-  const int nrows = min(wr, y_hi - wy0 + 1), ncols = min(wc, x_hi - wx0 + 1);
-  const bool col_in = lane < ncols;
-  const int gx = min(max(wx0 + lane, 0), W - 1);
-  const int u_lo = cu - RD, v_lo = cv - RD;
-  const int bx = u_lo - wx0, by = v_lo - wy0;  // window coordinates of candidate (0, 0)
-  const bool lane_in = active && bx >= 0 && bx + 2 * RD < ncols && by >= 0 && by + 2 * RD < nrows;
-  const bool outl = active && !lane_in;
+  w.nrows = min(wr, y_hi - w.wy0 + 1);
+  w.ncols = min(wc, x_hi - w.wx0 + 1);
+  w.col_in = lane < w.ncols;
+  w.lane_off = min(max(w.wx0 + lane, 0), t.W - 1) * (PLANAR ? 8 : 24);
+  return w;
+}
+
+// The wave's window outliers (outl: active lanes whose 49 candidates do not fit the window): deferred to the list, or
+// scored in place
+template <int D, bool PLANAR>
+__device__ __forceinline__ void level_outliers(const TileCtx& t, bool outl, bool& active, const h2* q, int& cu,
+                                               int& cv, h1& max_score) {
+  constexpr int F = 24;
+  const int lane = t.lane;
   const uint64_t om = __ballot(outl);
-#ifdef M3S_REFINE_STATS
-  if (lane == 0 && om) {
-    atomicAdd(&g_refine_stats[2 * D], (unsigned long long)__popcll(om));
-    atomicAdd(&g_refine_stats[2 * D + 1], 1ull);
-  }
-#endif
+  stats_outliers<D>(lane, om);
   if (om) {
     // a wave with a few window outliers scores them in place (one wave-level each, while the rest of the tile waits
     // at the next barrier); more than RT_INPLACE_MAX go to the deferred list (one wave per pixel in
@@ -466,7 +516,7 @@ __device__ __forceinline__ void refine_level(const TileCtx& t, bool& active, con
           const int v = __shfl(*reinterpret_cast<const int*>(&q[k]), src, 64);
           sq[k] = *reinterpret_cast<const h2*>(&v);
         }
-        wave_level<D, PLANAR>(t.img, H, W, sq, scu, scv, smax, lane);
+        wave_level<D, PLANAR>(t.img, t.H, t.W, sq, scu, scv, smax, lane);
         if (lane == src) {
           cu = scu;
           cv = scv;
@@ -475,216 +525,186 @@ __device__ __forceinline__ void refine_level(const TileCtx& t, bool& active, con
       }
     }
   }
-  // per-lane column offset; the row base (and the chunk plane) is wave-uniform (scalar)
-  const int lane_off = gx * (PLANAR ? 8 : F);
-  const size_t cstride = PLANAR ? (size_t)H * W * 8 : 8, rstride = (size_t)W * (PLANAR ? 8 : F);
-  if constexpr (SCREEN) {
-    float a[G * G];  // written by chunk 0's screen (seed): no zeroing
-#ifdef RT_NOCOMP
+}
+
+// The general window, one 8-channel chunk at a time: fill, wait, barrier, then score(chunk) in the lanes whose grid
+// lies in the window
+template <int D, bool PLANAR, class Scorer>
+__device__ __forceinline__ void general_window(const TileCtx& t, const LevelWin& w, uint4* lds, bool lane_in,
+                                               Scorer score) {
 #pragma unroll
-    for (int c = 0; c < G * G; c++) a[c] = 0.0f;
-#endif
-    __syncthreads();  // the reduction scratch aliases the window: its readers are done
-    rt_prio_from<RT_PRIO_START, RT_PRIO_FILL, D>();
-    if (packed) {  // (d = 1 only) the three chunk planes in one fill
-#ifndef RT_NOLOAD
-      for (int r = wid; r < 3 * nrows; r += RT_WAVES) {
-        const int chunk = r >= 2 * nrows ? 2 : (r >= nrows ? 1 : 0), y = r - chunk * nrows;
-        const int gy = min(max(wy0 + y, 0), H - 1);
-        const h1* rowp = t.img + (size_t)gy * rstride + chunk * cstride;
-        if (col_in)
-          __builtin_amdgcn_global_load_lds((gvoid_t)(rowp + lane_off),
-                                           (lvoid_t)&lds[chunk * RT_PPLANE + y * RT_PCOLS], 16, 0, 0);
-      }
-#endif
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __syncthreads();
-      rt_prio_from<RT_PRIO_FILL, RT_PRIO_SCORE, D>();
-#ifndef RT_NOCOMP
-      if (lane_in) {
-        const int b0 = by * RT_PCOLS + bx;
-        screen_chunk<D, RT_PCOLS>(&lds[b0], &q[0], a, true);
-        screen_chunk<D, RT_PCOLS>(&lds[RT_PPLANE + b0], &q[4], a);
-        screen_chunk<D, RT_PCOLS>(&lds[2 * RT_PPLANE + b0], &q[8], a);
-      }
-#endif
-    } else if (dbuf) {  // (d = 2 only) chunk c + 1 lands in the other buffer while chunk c is screened
-      auto fill = [&](int chunk, int buf) {
-#ifndef RT_NOLOAD
-        for (int y = wid; y < nrows; y += RT_WAVES) {
-          const int gy = min(max(wy0 + y, 0), H - 1);
-          const h1* rowp = t.img + (size_t)gy * rstride + chunk * cstride;
-          if (col_in) lds_dma_row(rowp + lane_off, t.lds_addr + (unsigned)(buf + y * RT_PCOLS) * 16u);
-        }
-#endif
-      };
-      const int b0 = by * RT_PCOLS + bx;
-      fill(0, 0);
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      // the same wait as a builtin: the compiler's wait model (blind to the asm) learns that none of its own loads
-      // (a previous level's survivor loads, spill reloads) is still in flight, so it places no vmcnt(0) of its own
-      // after fill(1), which would drain the DMA with them
-      __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0) expcnt(7) lgkmcnt(15)
-      __syncthreads();
-      fill(1, RT_DBUF);
-      rt_prio_from<RT_PRIO_FILL, RT_PRIO_SCORE, D>();
-#ifndef RT_NOCOMP
-      if (lane_in) screen_chunk<D, RT_PCOLS>(&lds[b0], &q[0], a, true);
-#endif
+  for (int chunk = 0; chunk < 3; chunk++) {
+    if (chunk) {
       rt_prio_from<RT_PRIO_SCORE, RT_PRIO_FILL, D>();
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __syncthreads();  // chunk 1 landed; every wave is done with buffer 0
-      fill(2, 0);
-      rt_prio_from<RT_PRIO_FILL, RT_PRIO_SCORE, D>();
-#ifndef RT_NOCOMP
-      if (lane_in) screen_chunk<D, RT_PCOLS>(&lds[RT_DBUF + b0], &q[4], a);
-#endif
-      rt_prio_from<RT_PRIO_SCORE, RT_PRIO_FILL, D>();
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __syncthreads();
-      rt_prio_from<RT_PRIO_FILL, RT_PRIO_SCORE, D>();
-#ifndef RT_NOCOMP
-      if (lane_in) screen_chunk<D, RT_PCOLS>(&lds[b0], &q[8], a);
-#endif
-    } else {
-#pragma unroll
-      for (int chunk = 0; chunk < F / 8; chunk++) {
-        if (chunk) {
-          rt_prio_from<RT_PRIO_SCORE, RT_PRIO_FILL, D>();
-          __syncthreads();
-        }
-#ifndef RT_NOLOAD
-        for (int y = wid; y < nrows; y += RT_WAVES) {
-          const int gy = min(max(wy0 + y, 0), H - 1);
-          const h1* rowp = t.img + (size_t)gy * rstride + chunk * cstride;
-          if (col_in)
-            __builtin_amdgcn_global_load_lds((gvoid_t)(rowp + lane_off), (lvoid_t)&lds[y * RT_COLS], 16, 0, 0);
-        }
-#endif
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        rt_prio_from<RT_PRIO_FILL, RT_PRIO_SCORE, D>();
-#ifndef RT_NOCOMP
-        if (lane_in) screen_chunk<D>(&lds[by * RT_COLS + bx], &q[chunk * 4], a, chunk == 0);
-#endif
-      }
+      __syncthreads();  // previous chunk's readers are done
     }
-    if (lane_in) {
-      uint64_t vm = (1ull << (G * G)) - 1ull;  // in-image candidates
-      if (__ballot(lane_in && !(u_lo >= 0 && u_lo + 6 * D < W && v_lo >= 0 && v_lo + 6 * D < H)) != 0) {
-        uint64_t jm = 0;
-#pragma unroll
-        for (int j = 0; j < G; j++) jm |= (v_lo + j * D >= 0 && v_lo + j * D < H) ? (1ull << j) : 0ull;
-        vm = 0;
-#pragma unroll
-        for (int i = 0; i < G; i++) vm |= (u_lo + i * D >= 0 && u_lo + i * D < W) ? (jm << (i * G)) : 0ull;
-        // out-of-image candidates scored clamped window pixels: they take no part in the level's best (nor survive)
-#pragma unroll
-        for (int c = 0; c < G * G; c++) a[c] = ((vm >> c) & 1ull) ? a[c] : -INFINITY;
-      }
-      // the level's best over the candidates that can win: after the first level the centre is dropped from the
-      // survivors (below), and it cannot raise T either: its exact score is the running max or a start pixel's <= +0,
-      // so a[centre] - 2B <= max_score - B, the other term of T
-      float lmax = a[0];
-#pragma unroll
-      for (int c = 1; c < G * G; c++)
-        if (c != G * G / 2) lmax = fmaxf(lmax, a[c]);
-      lmax = fmaxf(lmax, first ? a[G * G / 2] : -INFINITY);
-      // No lane of the wave can hold a survivor: the mask, the survivor loop and the re-centre are skipped as one
-      // wave-uniform branch. A lane's mask is non-empty exactly when lmax >= max_score - B: lmax is one of its
-      // candidates' a[c] and never below lmax - 2B, so it clears T = max(max_score - B, lmax - 2B) iff it clears the
-      // first term, and no candidate clears a T that lmax does not (a NaN lmax fails both tests). A lane without a
-      // usable bound (!sok: every candidate survives) keeps the wave out of the skip.
-      const float tms = (float)max_score - t.bq;
-      if (__builtin_amdgcn_readfirstlane((int)(__ballot(!t.sok || lmax >= tms) != 0ull)) == 0) return;
-      const float T = fmaxf(tms, lmax - 2.0f * t.bq);
-      uint64_t m = screen_mask(a, T);
-      if (!t.sok) m = ~0ull;
-      m &= vm;
-      if (!first) m &= ~(1ull << (G * G / 2));
-#ifdef M3S_REFINE_STATS  // survivors per level: lanes' sum [32 + 2D], per-wave maximum summed [33 + 2D]
-      {
-        int ns = __popcll(m), mx = ns;
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) mx = max(mx, __shfl_xor(mx, off, 64));
-        int sm = ns;
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) sm += __shfl_xor(sm, off, 64);
-        if (lane == __ffsll((long long)__ballot(1)) - 1) {
-          atomicAdd(&g_refine_stats[32 + 2 * D], (unsigned long long)sm);
-          atomicAdd(&g_refine_stats[33 + 2 * D], (unsigned long long)mx);
-        }
-      }
-#endif
-#ifdef RT_NOSURV
-      m = 0;
-#endif
-      int bi = -1;
-      if (packed)
-        exact_survivors_lds<D>(&lds[by * RT_PCOLS + bx], q, m, max_score, bi);
-      else
-        exact_survivors<D, PLANAR>(t.img, H, W, q, u_lo, v_lo, m, max_score, bi);
-      if (bi >= 0) {
-        cu = u_lo + (bi / G) * D;
-        cv = v_lo + (bi % G) * D;
-      }
-    }
-    return;
+    fill_rows<PLANAR, false>(t, w, lds, RT_COLS, chunk, t.wid);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    rt_prio_from<RT_PRIO_FILL, RT_PRIO_SCORE, D>();
+    if (lane_in) score(chunk);
   }
+}
+
+// A lane's in-image candidates (bit c = i * 7 + j: candidate (i, j) of the grid at u_lo, v_lo), and whether any lane
+// of the wave with its grid in the window has a candidate outside the image (wave-uniform)
+template <int D>
+__device__ __forceinline__ uint64_t in_image_mask(int u_lo, int v_lo, int H, int W) {
+  constexpr int G = 7;
+  uint64_t jm = 0, vm = 0;
+#pragma unroll
+  for (int j = 0; j < G; j++) jm |= (v_lo + j * D >= 0 && v_lo + j * D < H) ? (1ull << j) : 0ull;
+#pragma unroll
+  for (int i = 0; i < G; i++) vm |= (u_lo + i * D >= 0 && u_lo + i * D < W) ? (jm << (i * G)) : 0ull;
+  return vm;
+}
+template <int D>
+__device__ __forceinline__ bool wave_leaves_image(const LaneGrid& g, int H, int W) {
+  return __ballot(g.in && !(g.u_lo >= 0 && g.u_lo + 6 * D < W && g.v_lo >= 0 && g.v_lo + 6 * D < H)) != 0;
+}
+
+// The screened level (header comment of screen_chunk): fill by layout and screen, threshold, mask, exact chains of
+// the survivors, re-centre
+template <int D, bool PLANAR>
+__device__ __forceinline__ void screened_level(const TileCtx& t, const LevelWin& w, const LaneGrid& g, const h2* q,
+                                               int& cu, int& cv, h1& max_score, uint4* lds, bool first) {
+  constexpr int G = 7;
+  const int wid = t.wid, H = t.H, W = t.W;
+  float a[G * G];  // written by chunk 0's screen (seed): no zeroing
+  __syncthreads();  // the reduction scratch aliases the window: its readers are done
+  rt_prio_from<RT_PRIO_START, RT_PRIO_FILL, D>();
+  const int b0 = g.by * RT_PCOLS + g.bx;  // candidate (0, 0) in the 48-column layouts
+  if (w.packed) {  // (d = 1 only) the three chunk planes in one fill
+    // row r = chunk * nrows + y of the 3 * nrows goes to wave r % RT_WAVES: an even deal whatever nrows is
+    for (int chunk = 0; chunk < 3; chunk++)
+      fill_rows<PLANAR, false>(t, w, &lds[chunk * RT_PPLANE], RT_PCOLS, chunk,
+                               (wid - chunk * w.nrows) & (RT_WAVES - 1));
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    rt_prio_from<RT_PRIO_FILL, RT_PRIO_SCORE, D>();
+    if (g.in) {
+#pragma unroll
+      for (int chunk = 0; chunk < 3; chunk++)
+        screen_chunk<D, RT_PCOLS>(&lds[chunk * RT_PPLANE + b0], &q[chunk * 4], a, chunk == 0);
+    }
+  } else if (w.dbuf) {  // (d = 2 only) chunk c + 1 lands in the other buffer while chunk c is screened
+    fill_rows<PLANAR, true>(t, w, lds, RT_PCOLS, 0, wid);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    // the same wait as a builtin: the compiler's wait model (blind to the asm) learns that none of its own loads
+    // (a previous level's survivor loads, spill reloads) is still in flight, so it places no vmcnt(0) of its own
+    // after the next fill, which would drain the DMA with them
+    __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0) expcnt(7) lgkmcnt(15)
+    __syncthreads();
+#pragma unroll
+    for (int chunk = 0; chunk < 3; chunk++) {  // chunk is screened in buffer chunk & 1
+      if (chunk < 2) fill_rows<PLANAR, true>(t, w, &lds[((chunk + 1) & 1) * RT_DBUF], RT_PCOLS, chunk + 1, wid);
+      rt_prio_from<RT_PRIO_FILL, RT_PRIO_SCORE, D>();
+      if (g.in) screen_chunk<D, RT_PCOLS>(&lds[(chunk & 1) * RT_DBUF + b0], &q[chunk * 4], a, chunk == 0);
+      if (chunk < 2) {
+        rt_prio_from<RT_PRIO_SCORE, RT_PRIO_FILL, D>();
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();  // chunk + 1 landed; every wave is done with this chunk's buffer
+      }
+    }
+  } else {
+    general_window<D, PLANAR>(t, w, lds, g.in, [&](int chunk) {
+      screen_chunk<D>(&lds[g.by * RT_COLS + g.bx], &q[chunk * 4], a, chunk == 0);
+    });
+  }
+  if (g.in) {
+    uint64_t vm = (1ull << (G * G)) - 1ull;  // in-image candidates
+    if (wave_leaves_image<D>(g, H, W)) {
+      vm = in_image_mask<D>(g.u_lo, g.v_lo, H, W);
+      // out-of-image candidates scored clamped window pixels: they take no part in the level's best (nor survive)
+#pragma unroll
+      for (int c = 0; c < G * G; c++) a[c] = ((vm >> c) & 1ull) ? a[c] : -INFINITY;
+    }
+    // the level's best over the candidates that can win: after the first level the centre is dropped from the
+    // survivors (below), and it cannot raise T either: its exact score is the running max or a start pixel's <= +0,
+    // so a[centre] - 2B <= max_score - B, the other term of T
+    float lmax = a[0];
+#pragma unroll
+    for (int c = 1; c < G * G; c++)
+      if (c != G * G / 2) lmax = fmaxf(lmax, a[c]);
+    lmax = fmaxf(lmax, first ? a[G * G / 2] : -INFINITY);
+    // No lane of the wave can hold a survivor: the mask, the survivor loop and the re-centre are skipped as one
+    // wave-uniform branch. A lane's mask is non-empty exactly when lmax >= max_score - B: lmax is one of its
+    // candidates' a[c] and never below lmax - 2B, so it clears T = max(max_score - B, lmax - 2B) iff it clears the
+    // first term, and no candidate clears a T that lmax does not (a NaN lmax fails both tests). A lane without a
+    // usable bound (!sok: every candidate survives) keeps the wave out of the skip.
+    const float tms = (float)max_score - t.bq;
+    if (__builtin_amdgcn_readfirstlane((int)(__ballot(!t.sok || lmax >= tms) != 0ull)) == 0) return;
+    const float T = fmaxf(tms, lmax - 2.0f * t.bq);
+    uint64_t m = screen_mask(a, T);
+    if (!t.sok) m = ~0ull;
+    m &= vm;
+    if (!first) m &= ~(1ull << (G * G / 2));
+    stats_survivors<D>(t.lane, m);
+    int bi = -1;
+    if (w.packed)
+      exact_survivors_lds<D>(&lds[b0], q, m, max_score, bi);
+    else
+      exact_survivors<D, PLANAR>(t.img, H, W, q, g.u_lo, g.v_lo, m, max_score, bi);
+    recentre<D>(g, bi, cu, cv);
+  }
+}
+
+// The exact scan's step over the 49 scores, in scan order (u outer, v inner), strict '>'. MASKED: only the candidates
+// of vm take part
+template <bool MASKED>
+__device__ __forceinline__ void exact_scan(const h1* s, uint64_t vm, h1& max_score, int& bi) {
+#pragma unroll
+  for (int c = 0; c < 49; c++) {
+    const bool gt = (!MASKED || ((vm >> c) & 1ull)) && s[c] > max_score;
+    max_score = gt ? s[c] : max_score;
+    bi = gt ? c : bi;
+  }
+}
+
+// The exact level: all 49 candidates by the c10::Half chain, the running sums in registers across the three chunks
+template <int D, bool PLANAR>
+__device__ __forceinline__ void exact_level(const TileCtx& t, const LevelWin& w, const LaneGrid& g, const h2* q,
+                                            int& cu, int& cv, h1& max_score, uint4* lds) {
+  constexpr int G = 7;
   h1 s[G * G];
 #pragma unroll
   for (int c = 0; c < G * G; c++) s[c] = (h1)0.0f;
   __syncthreads();  // the reduction scratch aliases the window: its readers are done
   rt_prio_from<RT_PRIO_START, RT_PRIO_FILL, D>();
-#pragma unroll
-  for (int chunk = 0; chunk < F / 8; chunk++) {
-    if (chunk) {
-      rt_prio_from<RT_PRIO_SCORE, RT_PRIO_FILL, D>();
-      __syncthreads();  // previous chunk's readers are done
-    }
-#ifndef RT_NOLOAD
-    for (int y = wid; y < nrows; y += RT_WAVES) {  // one global_load_lds (64 lanes x 16 B) per window row
-      const int gy = min(max(wy0 + y, 0), H - 1);
-      const h1* rowp = t.img + (size_t)gy * rstride + chunk * cstride;
-      if (col_in) __builtin_amdgcn_global_load_lds((gvoid_t)(rowp + lane_off), (lvoid_t)&lds[y * RT_COLS], 16, 0, 0);
-    }
-#endif
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    rt_prio_from<RT_PRIO_FILL, RT_PRIO_SCORE, D>();
-#ifndef RT_NOCOMP
-    if (lane_in) score_chunk<D>(&lds[by * RT_COLS + bx], &q[chunk * 4], s);
-#endif
-  }
-  if (lane_in) {  // scan-order arg-max: u outer, v inner, strict '>' (matching_kernels.cu:54-71)
+  general_window<D, PLANAR>(t, w, lds, g.in, [&](int chunk) {
+    score_chunk<D>(&lds[g.by * RT_COLS + g.bx], &q[chunk * 4], s);
+  });
+  if (g.in) {  // scan-order arg-max: u outer, v inner, strict '>' (matching_kernels.cu:54-71)
     int bi = -1;
-    if (__ballot(lane_in && !(u_lo >= 0 && u_lo + 6 * D < W && v_lo >= 0 && v_lo + 6 * D < H)) == 0) {
-      // every candidate grid of the wave lies inside the image: index-only tracking
-#pragma unroll
-      for (int c = 0; c < G * G; c++) {
-        const bool gt = s[c] > max_score;
-        max_score = gt ? s[c] : max_score;
-        bi = gt ? c : bi;
-      }
-    } else {
-#pragma unroll
-      for (int i = 0; i < G; i++) {
-        const bool uok = u_lo + i * D >= 0 && u_lo + i * D < W;
-#pragma unroll
-        for (int j = 0; j < G; j++) {
-          const bool vok = v_lo + j * D >= 0 && v_lo + j * D < H;
-          const bool gt = uok && vok && s[i * G + j] > max_score;
-          max_score = gt ? s[i * G + j] : max_score;
-          bi = gt ? i * G + j : bi;
-        }
-      }
-    }
-    if (bi >= 0) {
-      cu = u_lo + (bi / G) * D;
-      cv = v_lo + (bi % G) * D;
-    }
+    // every candidate grid of the wave lies inside the image (nearly every wave): index-only tracking, no mask test
+    if (!wave_leaves_image<D>(g, t.H, t.W))
+      exact_scan<false>(s, 0ull, max_score, bi);
+    else
+      exact_scan<true>(s, in_image_mask<D>(g.u_lo, g.v_lo, t.H, t.W), max_score, bi);
+    recentre<D>(g, bi, cu, cv);
   }
 }
+
+// One level of the tile: window, outliers, then the screened or the exact scoring of the lanes in the window
+template <int D, bool SCREEN, bool PLANAR>
+__device__ __forceinline__ void refine_level(const TileCtx& t, bool& active, const h2* q, int& cu, int& cv,
+                                             h1& max_score, uint4* lds, int (*s_red)[4], bool first) {
+  constexpr int RD = 3 * D;
+  rt_prio<RT_PRIO_START, D>();  // three other waves wait at the exchange's barriers
+  const LevelWin w = level_window<D, SCREEN, PLANAR>(t, active, cu, cv, s_red);
+  LaneGrid g;
+  g.u_lo = cu - RD;
+  g.v_lo = cv - RD;
+  g.bx = g.u_lo - w.wx0;
+  g.by = g.v_lo - w.wy0;
+  g.in = active && g.bx >= 0 && g.bx + 2 * RD < w.ncols && g.by >= 0 && g.by + 2 * RD < w.nrows;
+  level_outliers<D, PLANAR>(t, active && !g.in, active, q, cu, cv, max_score);
+  if constexpr (SCREEN)
+    screened_level<D, PLANAR>(t, w, g, q, cu, cv, max_score, lds, first);
+  else
+    exact_level<D, PLANAR>(t, w, g, q, cu, cv, max_score, lds);
+}
+
 
 template <bool P1_I64>
 __device__ __forceinline__ void load_p1(const void* p1v, size_t bn, int& cu, int& cv) {
@@ -707,19 +727,6 @@ __device__ __forceinline__ void store_out(void* outv, size_t bn, int W, int cu, 
   }
 }
 
-// Where the FUSE_PROJ instance issues the six loads of its D21 row (vmcnt retires in order: once they are issued, the
-// wave's next wait on an LM gather waits for them too). 0: at kernel start; 1: staggered, block b behind LM iteration
-// 1 + b % RT_D21_K, so the 1024 resident blocks' 25 MB trickle in under the latency-bound LM phase; 2 (shipped):
-// behind the LM loop, their latency under the tile-flow exchange. The blocks leave the LM loop 16 to 31 us after the
-// launch starts, which spreads the loads by itself. Measured (profiles/match_fuse_proj_ab.json, alternating bench
-// runs on four boxes): 2 is the fastest and the steadiest, 1 within 1 us of it with slow runs, 0 slowest.
-#ifndef RT_D21_PLACE
-#define RT_D21_PLACE 2
-#endif
-#ifndef RT_D21_K
-#define RT_D21_K 8
-#endif
-
 // The projection search's arguments of the FUSE_PROJ instance (proj_occlusion_kernel's, matching.hip)
 struct ProjArgs {
   const float* rays9;        // (B,H,W,9) prep_rays_kernel's ray image
@@ -732,6 +739,100 @@ struct ProjArgs {
   float lambda_init, cost_thresh, dist_thresh;
 };
 
+// The FUSE_PROJ prologue: the lane projects its own pixel (centre -> cu, cv), writes valid and leaves the six loads
+// of its raw D21 row (dv) in flight; SCREEN: wave 0 reduces prep's norm partials (cmax_w).
+template <bool SCREEN>
+__device__ __forceinline__ void proj_prologue(const TileCtx& t, const ProjArgs& pa, const void* D21, int b,
+                                              bool active, size_t bn, int& cu, int& cv, float4* dv, float& cmax_w) {
+  constexpr int F = 24;
+  const int H = t.H, W = t.W, N = H * W;
+  // the LM gathers and the D21 row loads behind them (until the first level's start sets its own)
+  rt_prio_from<0, RT_PRIO_LM, 0>();
+  // a lane past the image projects the nearest pixel inside it (every address stays in bounds, no branch join in
+  // front of the loads) and writes nothing
+  const int n = min(t.v_pix, H - 1) * W + min(t.u_pix, W - 1);
+  const size_t bnc = (size_t)b * N + n;
+  const float x = pa.X21[bnc * 3 + 0], y = pa.X21[bnc * 3 + 1], z = pa.X21[bnc * 3 + 2];
+  const int64_t i0 = pa.idx_init != nullptr ? pa.idx_init[bnc] : (int64_t)n;
+  if constexpr (SCREEN) {
+    // reduce_cnorm's loads, in flight beside the pixel's own (4 KB from L2 at 512x512)
+    if (t.wid == 0) cmax_w = reduce_cnorm_wave(pa.cnorm_part, pa.nparts);
+  }
+  const float nrm = fmaxf(norm3_ref(x, y, z), 1e-12f);  // F.normalize (matching.py:44)
+  const float p[3] = {x / nrm, y / nrm, z / nrm};
+  float u, v;
+  lin_to_pixel_f(i0, W, u, v);
+  bool conv = false;
+  float Xg[3];  // X11 at the final pixel, gathered during the last LM iteration
+  iter_proj_point<true>(pa.rays9 + (size_t)b * N * 9, H, W, p, u, v, conv, pa.max_iter, pa.lambda_init,
+                        pa.cost_thresh, pa.X11 + (size_t)b * N * 3, Xg);
+  // The six loads of the D21 row are issued here, behind the LM loop (vmcnt retires in order: once they are issued,
+  // the wave's next wait on an LM gather waits for them too); their latency runs under the tile-flow exchange. The
+  // blocks leave the LM loop 16 to 31 us after the launch starts, which spreads the 1024 resident blocks' 25 MB by
+  // itself. Measured (profiles/match_fuse_proj_ab.json, alternating bench runs on four boxes): the fastest and the
+  // steadiest placement; staggered behind the LM iterations within 1 us of it with slow runs, at kernel start slowest.
+  const float4* qsrc = reinterpret_cast<const float4*>(reinterpret_cast<const float*>(D21) + bnc * F);
+#pragma unroll
+  for (int k = 0; k < F / 4; k++) dv[k] = qsrc[k];
+  cu = (int)u;  // .long() truncation; u, v >= 1 after clamping
+  cv = (int)v;
+  // (every lane: a branch here would leave Xg's gather pending in the lanes past the image, and the next write of
+  // its registers would drain the D21 loads with it)
+  const float dx = Xg[0] - x, dy = Xg[1] - y, dz = Xg[2] - z;
+  const float d = norm3_ref(dx, dy, dz);  // torch.linalg.norm (matching.py:71-73)
+  const uint8_t vbyte = conv && (d < pa.dist_thresh);
+  if (active) pa.valid[bn] = vbyte;
+}
+
+// Tile flow estimate, once per tile: the centres move by at most 3d per level, well inside the +-16 px inlier band, so
+// the initial mean serves every level (saves a block reduction per level). Sets t.fu / t.fv and t.tcu / t.tcv.
+// XCHG_CMAX: the same exchange hands wave 0's cmax_w to every wave (the return value).
+template <bool XCHG_CMAX>
+__device__ __forceinline__ float tile_flow(TileCtx& t, bool active, int cu, int cv, int tx, int ty, float cmax_w,
+                                           int (*s_red)[4]) {
+  float cmax_b = 0.0f;
+  int su = active ? cu - t.u_pix : 0, sv = active ? cv - t.v_pix : 0, na = active ? 1 : 0;
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    su += __shfl_xor(su, off, 64);
+    sv += __shfl_xor(sv, off, 64);
+    na += __shfl_xor(na, off, 64);
+  }
+  if (t.lane == 0) {
+    s_red[t.wid][0] = su;
+    s_red[t.wid][1] = sv;
+    s_red[t.wid][2] = na;
+    if constexpr (XCHG_CMAX) s_red[t.wid][3] = __float_as_int(cmax_w);
+  }
+  __syncthreads();
+  if constexpr (XCHG_CMAX) cmax_b = __int_as_float(__builtin_amdgcn_readfirstlane(s_red[0][3]));
+  // block-uniform: SGPRs (readfirstlane), not VGPRs live across every level
+  int tu = 0, tv = 0, tn = 0;
+#pragma unroll
+  for (int w = 0; w < RT_WAVES; w++) {
+    tu += s_red[w][0];
+    tv += s_red[w][1];
+    tn += s_red[w][2];
+  }
+  const int nall = max(1, tn);
+  t.fu = __builtin_amdgcn_readfirstlane(tu / nall);
+  t.fv = __builtin_amdgcn_readfirstlane(tv / nall);
+  t.tcu = tx * RT_TW + RT_TW / 2 + t.fu;
+  t.tcv = ty * RT_TH + RT_TH / 2 + t.fv;
+  return cmax_b;
+}
+
+// SCREEN: the lane's bound B from its query's norm and the descriptor-norm bound cm (t.bq, t.sok; derivation in the
+// header comment of screen_chunk)
+__device__ __forceinline__ void screen_bound(TileCtx& t, const h2* q, float cm) {
+  float qq = 0.0f;
+#pragma unroll
+  for (int k = 0; k < 12; k++) qq = __builtin_amdgcn_fdot2(q[k], q[k], qq, false);
+  const float pq = sqrtf(qq) * cm * 1.001f;  // |q|_2 |c|_2 bound, rounded up
+  t.sok = pq <= 16384.0f;                         // false for NaN / inf
+  t.bq = t.sok ? 0.0125f * pq + 0x1p-18f : 0.0f;
+}
+
 // P1_I64: p1 given as (B,N,2) int64 (reference op) else int32 (fused); LIN_OUT: write idx = u + W v.
 // SCREEN: bound-screened scoring (cmaxp = the descriptor-norm bound written by prep / proj_occlusion).
 // LIN_OUT (fused path) reads the PLANAR D11h of prep_rays_kernel.
@@ -740,22 +841,14 @@ struct ProjArgs {
 // centre in registers (no p1 traffic), writes valid and goes on into the levels; one wave per block reduces prep's
 // norm partials itself (no launch sits between prep and this one; the max is order-independent, so every block gets
 // the same bits). Runs without a deferred list only (olist == nullptr: nothing clears ocount in front of it).
-#ifndef RT_MIN_BLOCKS  // blocks per CU the register budget is sized for (16 waves: 128 VGPRs, the LDS limit too)
-#define RT_MIN_BLOCKS (16 / RT_WAVES)
-#endif
 template <bool D21_F32, bool P1_I64, bool LIN_OUT, bool SCREEN, bool FUSE_PROJ = false>
-__global__ void __launch_bounds__(RT_THREADS, RT_MIN_BLOCKS) refine_tile_kernel(const h1* __restrict__ D11h, const void* __restrict__ D21,
-                                                             const void* __restrict__ p1v, void* __restrict__ outv,
-                                                             int H, int W, int dilation_max, int tiles_x,
-                                                             int tiles_per_img, int nblocks, int4* olist,
-                                                             int* ocount, const float* __restrict__ cmaxp,
-                                                             const ProjArgs pa) {
+__global__ void __launch_bounds__(RT_THREADS, RT_MIN_BLOCKS)
+    refine_tile_kernel(const h1* __restrict__ D11h, const void* __restrict__ D21, const void* __restrict__ p1v,
+                       void* __restrict__ outv, int H, int W, int dilation_max, int tiles_x, int tiles_per_img,
+                       int nblocks, int4* olist, int* ocount, const float* __restrict__ cmaxp, const ProjArgs pa) {
   constexpr int F = 24;
   static_assert(!FUSE_PROJ || (D21_F32 && !P1_I64 && LIN_OUT), "the fused projection feeds the fused match path");
-#ifdef M3S_REFINE_BSTAMPS
-  const unsigned long long stamp_top = __builtin_amdgcn_s_memrealtime();
-  unsigned long long stamp_lm = 0;
-#endif
+  const unsigned long long stamp_top = bstamp_clock();
   __shared__ uint4 lds[RT_ROWS * RT_COLS];
   int(*s_red)[4] = reinterpret_cast<int(*)[4]>(&lds[0]);  // level-start reductions alias the window
   const int lb = xcd_remap(blockIdx.x, nblocks);
@@ -777,7 +870,6 @@ __global__ void __launch_bounds__(RT_THREADS, RT_MIN_BLOCKS) refine_tile_kernel(
   }
   t.olist = olist;
   t.ocount = ocount;
-  t.lds_addr = (unsigned)(uintptr_t)(lvoid_t)lds;
   bool active = t.u_pix < W && t.v_pix < H;
   const int N = H * W;
   const size_t bn = (size_t)b * N + (size_t)t.v_pix * W + t.u_pix;
@@ -788,55 +880,7 @@ __global__ void __launch_bounds__(RT_THREADS, RT_MIN_BLOCKS) refine_tile_kernel(
   float4 dv[F / 4];   // FUSE_PROJ: the raw D21 row, converted where it is first needed
   float cmax_w = 0.0f;  // FUSE_PROJ && SCREEN: the descriptor-norm bound, held by wave 0 until the tile-flow exchange
   if constexpr (FUSE_PROJ) {
-    // the LM gathers and the D21 row loads behind them (until the first level's start sets its own)
-    rt_prio_from<0, RT_PRIO_LM, 0>();
-    // a lane past the image projects the nearest pixel inside it (every address stays in bounds, no branch join in
-    // front of the loads) and writes nothing
-    const int n = min(t.v_pix, H - 1) * W + min(t.u_pix, W - 1);
-    const size_t bnc = (size_t)b * N + n;
-    const float4* qsrc = reinterpret_cast<const float4*>(reinterpret_cast<const float*>(D21) + bnc * F);
-    auto issue_q = [&]() {
-#pragma unroll
-      for (int k = 0; k < F / 4; k++) dv[k] = qsrc[k];
-    };
-    if constexpr (RT_D21_PLACE == 0) issue_q();
-    const float x = pa.X21[bnc * 3 + 0], y = pa.X21[bnc * 3 + 1], z = pa.X21[bnc * 3 + 2];
-    const int64_t i0 = pa.idx_init != nullptr ? pa.idx_init[bnc] : (int64_t)n;
-    if constexpr (SCREEN) {
-      // reduce_cnorm's loads, in flight beside the pixel's own (4 KB from L2 at 512x512)
-      if (t.wid == 0) cmax_w = reduce_cnorm_wave(pa.cnorm_part, pa.nparts);
-    }
-    const float nrm = fmaxf(norm3_ref(x, y, z), 1e-12f);  // F.normalize (matching.py:44)
-    const float p[3] = {x / nrm, y / nrm, z / nrm};
-    float u, v;
-    lin_to_pixel_f(i0, W, u, v);
-    bool conv = false;
-    float Xg[3];  // X11 at the final pixel, gathered during the last LM iteration
-    // wave-uniform (scalar) test: a per-lane branch inside the LM loop is costly
-    const int slot = (int)(blockIdx.x % RT_D21_K);
-    auto after_iter = [&](int i) {
-      if constexpr (RT_D21_PLACE == 1) {
-        if (i == slot) issue_q();
-      }
-    };
-    iter_proj_point<true>(pa.rays9 + (size_t)b * N * 9, H, W, p, u, v, conv, pa.max_iter, pa.lambda_init,
-                          pa.cost_thresh, pa.X11 + (size_t)b * N * 3, Xg, after_iter);
-    if constexpr (RT_D21_PLACE == 2) issue_q();
-    cu = (int)u;  // .long() truncation; u, v >= 1 after clamping
-    cv = (int)v;
-    // (every lane: a branch here would leave Xg's gather pending in the lanes past the image, and the next write of
-    // its registers would drain the D21 loads with it)
-    const float dx = Xg[0] - x, dy = Xg[1] - y, dz = Xg[2] - z;
-    const float d = norm3_ref(dx, dy, dz);  // torch.linalg.norm (matching.py:71-73)
-    const uint8_t vbyte = conv && (d < pa.dist_thresh);
-    if (active) pa.valid[bn] = vbyte;
-    if constexpr (RT_D21_PLACE == 1) {
-      // fewer LM iterations than this block's slot: behind Xg's use, so its wait does not cover these loads
-      if (slot >= pa.max_iter - 1) issue_q();
-    }
-#ifdef M3S_REFINE_BSTAMPS
-    stamp_lm = __builtin_amdgcn_s_memrealtime();
-#endif
+    proj_prologue<SCREEN>(t, pa, D21, b, active, bn, cu, cv, dv, cmax_w);
   } else if (active) {
     load_query<F, D21_F32>(D21, bn, q);
     load_p1<P1_I64>(p1v, bn, cu, cv);
@@ -844,38 +888,9 @@ __global__ void __launch_bounds__(RT_THREADS, RT_MIN_BLOCKS) refine_tile_kernel(
 #pragma unroll
     for (int k = 0; k < F / 2; k++) q[k] = h2{(h1)0.0f, (h1)0.0f};
   }
-  float cmax_b = 0.0f;  // FUSE_PROJ && SCREEN: wave 0's cmax_w, for every wave
-  {  // tile flow estimate, once per tile: the centres move by at most 3d per level, well inside the
-     // +-16 px inlier band, so the initial mean serves every level (saves a block reduction per level)
-    int su = active ? cu - t.u_pix : 0, sv = active ? cv - t.v_pix : 0, na = active ? 1 : 0;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-      su += __shfl_xor(su, off, 64);
-      sv += __shfl_xor(sv, off, 64);
-      na += __shfl_xor(na, off, 64);
-    }
-    if (t.lane == 0) {
-      s_red[t.wid][0] = su;
-      s_red[t.wid][1] = sv;
-      s_red[t.wid][2] = na;
-      if constexpr (FUSE_PROJ && SCREEN) s_red[t.wid][3] = __float_as_int(cmax_w);
-    }
-    __syncthreads();
-    if constexpr (FUSE_PROJ && SCREEN) cmax_b = __int_as_float(__builtin_amdgcn_readfirstlane(s_red[0][3]));
-    // block-uniform: SGPRs (readfirstlane), not VGPRs live across every level
-    int tu = 0, tv = 0, tn = 0;
-#pragma unroll
-    for (int w = 0; w < RT_WAVES; w++) {
-      tu += s_red[w][0];
-      tv += s_red[w][1];
-      tn += s_red[w][2];
-    }
-    const int nall = max(1, tn);
-    t.fu = __builtin_amdgcn_readfirstlane(tu / nall);
-    t.fv = __builtin_amdgcn_readfirstlane(tv / nall);
-    t.tcu = tx * RT_TW + RT_TW / 2 + t.fu;
-    t.tcv = ty * RT_TH + RT_TH / 2 + t.fv;
-  }
+  const unsigned long long stamp_lm = bstamp_clock();  // FUSE_PROJ: the LM phase's end
+  // FUSE_PROJ && SCREEN: wave 0's cmax_w, for every wave
+  const float cmax_b = tile_flow<FUSE_PROJ && SCREEN>(t, active, cu, cv, tx, ty, cmax_w, s_red);
   if constexpr (FUSE_PROJ) {
     // the D21 row, f32 -> f16 (RNE, == torch .half(): load_query's conversion) behind the tile-flow exchange: the
     // loads' latency runs under it
@@ -885,24 +900,9 @@ __global__ void __launch_bounds__(RT_THREADS, RT_MIN_BLOCKS) refine_tile_kernel(
       q[2 * k + 1] = h2{(h1)dv[k].z, (h1)dv[k].w};
     }
   }
-  t.bq = 0.0f;
-  t.sok = false;
-  if constexpr (SCREEN) {
-    float qq = 0.0f;
-#pragma unroll
-    for (int k = 0; k < F / 2; k++) qq = __builtin_amdgcn_fdot2(q[k], q[k], qq, false);
-    float cm;
-    if constexpr (FUSE_PROJ) cm = cmax_b; else cm = *cmaxp;
-    const float pq = sqrtf(qq) * cm * 1.001f;  // |q|_2 |c|_2 bound, rounded up
-    t.sok = pq <= 16384.0f;                         // false for NaN / inf
-    t.bq = t.sok ? 0.0125f * pq + 0x1p-18f : 0.0f;
-  }
+  if constexpr (SCREEN) screen_bound(t, q, FUSE_PROJ ? cmax_b : *cmaxp);
   const bool mine = active;  // deferred pixels are written by refine_outlier_kernel
-#ifdef M3S_REFINE_BSTAMPS
-  // the unfused instance: the levels' start; FUSE_PROJ: the kernel's first instruction (the LM phase's end: slot 3)
-  if (threadIdx.x == 0 && blockIdx.x < 8192)
-    g_refine_bstamps[blockIdx.x * 4 + 0] = FUSE_PROJ ? stamp_top : __builtin_amdgcn_s_memrealtime();
-#endif
+  bstamp_levels_start(FUSE_PROJ, stamp_top);
   h1 max_score = (h1)0.0f;   // numeric_limits<c10::Half>::min() == +0, never reset between levels
   // the levels as straight-line code (d = dilation_max .. 1) instead of a loop over a switch of the eight inlined level
   // bodies: across that loop's back edge the register allocator made ~800 copies and spilled 19 VGPRs (80 B of scratch
@@ -922,24 +922,7 @@ __global__ void __launch_bounds__(RT_THREADS, RT_MIN_BLOCKS) refine_tile_kernel(
 #undef RT_LEVEL
   rt_prio<0>();
   if (mine && active) store_out<LIN_OUT>(outv, bn, W, cu, cv);
-#ifdef M3S_REFINE_BSTAMPS
-  const unsigned long long nact = __popcll(__ballot(active));
-  // aliases the window (done with): a separate __shared__ array would push the block past 40 KiB of LDS and
-  // change the occupancy being measured (4 -> 3 blocks per CU)
-  unsigned long long* s_act = reinterpret_cast<unsigned long long*>(&lds[0]);
-  __syncthreads();
-  if (t.lane == 0) s_act[t.wid] = nact;
-  __syncthreads();
-  if (threadIdx.x == 0 && blockIdx.x < 8192) {
-    unsigned hw;
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
-    g_refine_bstamps[blockIdx.x * 4 + 1] = __builtin_amdgcn_s_memrealtime();
-    g_refine_bstamps[blockIdx.x * 4 + 2] = hw;
-    unsigned long long na = 0;
-    for (int w = 0; w < RT_WAVES; w++) na += s_act[w];
-    g_refine_bstamps[blockIdx.x * 4 + 3] = FUSE_PROJ ? stamp_lm : na;  // FUSE_PROJ: when the LM phase ended
-  }
-#endif
+  bstamp_block_end(FUSE_PROJ, stamp_lm, active, lds);
 }
 
 // Finishes the deferred pixels: one wave per pixel, levels d0..1 by wave_level (grid-stride over
@@ -980,6 +963,17 @@ __global__ void __launch_bounds__(256) refine_outlier_kernel(const h1* __restric
   }
 }
 
+// One launch of a tile instance: one block per 32 x 8 tile of every image
+template <bool D21_F32, bool P1_I64, bool LIN_OUT, bool SCREEN, bool FUSE_PROJ>
+static void launch_tile(const void* D11h, const void* D21, const void* p1, void* out, int B, int H, int W,
+                        int dilation_max, int4* olist, int* ocount, const float* cmax, const ProjArgs& pa,
+                        hipStream_t s) {
+  const int tx = (W + RT_TW - 1) / RT_TW, ty = (H + RT_TH - 1) / RT_TH, nb = tx * ty * B;
+  hipLaunchKernelGGL((refine_tile_kernel<D21_F32, P1_I64, LIN_OUT, SCREEN, FUSE_PROJ>), dim3(nb), dim3(RT_THREADS), 0,
+                     s, reinterpret_cast<const h1*>(D11h), D21, p1, out, H, W, dilation_max, tx, tx * ty, nb, olist,
+                     ocount, cmax, pa);
+}
+
 }  // namespace m3s
 
 // shapes the tile kernel takes (else the per-pixel kernels of matching.hip); the fused path's prep writes the
@@ -998,19 +992,18 @@ extern "C" hipError_t m3s_launch_refine_tile(const void* D11h, const void* D21, 
                                              int H, int W, int F, int radius, int dilation_max, int fused,
                                              void* olist, int* ocount, const float* cmax, hipStream_t s) {
   if (!m3s_refine_tile_ok(B, H, W, F, radius, dilation_max)) return hipErrorNotSupported;
-  const int tx = (W + RT_TW - 1) / RT_TW, ty = (H + RT_TH - 1) / RT_TH, nb = tx * ty * B;
   const m3s::h1* a = reinterpret_cast<const m3s::h1*>(D11h);
   int4* ol = reinterpret_cast<int4*>(olist);
   if (ol == nullptr) ocount = nullptr;
+  const m3s::ProjArgs none{};
   if (fused && cmax != nullptr)
-    hipLaunchKernelGGL((m3s::refine_tile_kernel<true, false, true, true>), dim3(nb), dim3(RT_THREADS), 0, s, a, D21, p1,
-                       out, H, W, dilation_max, tx, tx * ty, nb, ol, ocount, cmax, m3s::ProjArgs{});
+    m3s::launch_tile<true, false, true, true, false>(a, D21, p1, out, B, H, W, dilation_max, ol, ocount, cmax, none, s);
   else if (fused)
-    hipLaunchKernelGGL((m3s::refine_tile_kernel<true, false, true, false>), dim3(nb), dim3(RT_THREADS), 0, s, a, D21, p1,
-                       out, H, W, dilation_max, tx, tx * ty, nb, ol, ocount, nullptr, m3s::ProjArgs{});
+    m3s::launch_tile<true, false, true, false, false>(a, D21, p1, out, B, H, W, dilation_max, ol, ocount, nullptr,
+                                                      none, s);
   else
-    hipLaunchKernelGGL((m3s::refine_tile_kernel<false, true, false, false>), dim3(nb), dim3(RT_THREADS), 0, s, a, D21,
-                       p1, out, H, W, dilation_max, tx, tx * ty, nb, ol, ocount, nullptr, m3s::ProjArgs{});
+    m3s::launch_tile<false, true, false, false, false>(a, D21, p1, out, B, H, W, dilation_max, ol, ocount, nullptr,
+                                                       none, s);
   if (ol != nullptr) {
     // 1024 waves: the list is empty or short once waves score up to RT_INPLACE_MAX outliers in place (a smaller
     // grid launches and drains faster); pathological inputs (every lane an outlier) take several passes
@@ -1037,18 +1030,14 @@ extern "C" hipError_t m3s_launch_refine_tile_proj(const void* D11h, const float*
                                                   hipStream_t s) {
   if (!m3s_refine_tile_ok(B, H, W, F, radius, dilation_max)) return hipErrorNotSupported;
   if ((size_t)9 * H * W >= ((size_t)1 << 31)) return hipErrorNotSupported;  // bilin_sample9's 32-bit offsets
-  const int tx = (W + RT_TW - 1) / RT_TW, ty = (H + RT_TH - 1) / RT_TH, nb = tx * ty * B;
-  const m3s::h1* a = reinterpret_cast<const m3s::h1*>(D11h);
   const m3s::ProjArgs pa{rays9, X11, X21, idx_init, valid, cnorm_part, nparts, max_iter, lambda_init, cost_thresh,
                          dist_thresh};
   if (cnorm_part != nullptr)
-    hipLaunchKernelGGL((m3s::refine_tile_kernel<true, false, true, true, true>), dim3(nb), dim3(RT_THREADS), 0, s, a,
-                       (const void*)D21, (const void*)nullptr, (void*)idx_out, H, W, dilation_max, tx, tx * ty, nb,
-                       (int4*)nullptr, (int*)nullptr, (const float*)nullptr, pa);
+    m3s::launch_tile<true, false, true, true, true>(D11h, D21, nullptr, idx_out, B, H, W, dilation_max, nullptr,
+                                                    nullptr, nullptr, pa, s);
   else
-    hipLaunchKernelGGL((m3s::refine_tile_kernel<true, false, true, false, true>), dim3(nb), dim3(RT_THREADS), 0, s, a,
-                       (const void*)D21, (const void*)nullptr, (void*)idx_out, H, W, dilation_max, tx, tx * ty, nb,
-                       (int4*)nullptr, (int*)nullptr, (const float*)nullptr, pa);
+    m3s::launch_tile<true, false, true, false, true>(D11h, D21, nullptr, idx_out, B, H, W, dilation_max, nullptr,
+                                                     nullptr, nullptr, pa, s);
   return hipGetLastError();
 }
 

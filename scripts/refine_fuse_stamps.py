@@ -1,6 +1,7 @@
 """Per-block stamps of the fused projection + refine launch (a -DM3S_REFINE_BSTAMPS build of refine.hip, chosen with
-M3S_LIB; -DRT_D21_PLACE=0|1|2 picks where the D21 row loads are issued): kernel span, block durations and the split
-into the LM phase (kernel start -> projection done) and the rest (tile flow, levels, store) at 512x512."""
+M3S_LIB): kernel span, block durations and the split into the LM phase (kernel start -> projection done) and the rest
+(tile flow, levels, store) at 512x512. The D21 row loads are issued behind the LM loop; the placements it was compared
+with (profiles/match_fuse_proj_trace.txt) build at the tag refine-experiments-r6."""
 import ctypes
 import os
 import sys

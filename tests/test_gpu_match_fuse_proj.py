@@ -104,6 +104,26 @@ def test_scattered_warm_start(monkeypatch, scattered, inplace):
     _assert_same(un, fu, ref)
 
 
+def test_deferred_from_the_coarsest_levels(monkeypatch):
+    """dilation_max = 8: at d = 8 and d = 7 no grid fits the 40-row window (6 d >= 42), so with M3S_REFINE_INPLACE=0
+    every wave defers all its lanes at the first level and refine_outlier_kernel runs levels 8 .. 1. White unit
+    descriptors: each coarse level moves most pixels (the oracle's dilation_max 8 and 7 results differ on 74 % of
+    them; with the smooth synthetic descriptors they are identical), so a dropped or mis-ordered level shows."""
+    from m3s.config import config
+
+    config["matching"]["dilation_max"] = 8
+    X11, X21, _, _ = _pairs(1, 16, 64, seed=60)
+    rng = np.random.default_rng(8)
+    D11, D21 = (rng.standard_normal((1, 16, 64, 24)) for _ in range(2))
+    D11, D21 = ((d / np.linalg.norm(d, axis=-1, keepdims=True)).astype(np.float32) for d in (D11, D21))
+    args = [_dev(X11), _dev(X21), _dev(D11), _dev(D21)]
+    ref = O.match(X11, X21, D11, D21, dilation_max=8)
+    monkeypatch.setenv("M3S_REFINE_INPLACE", "0")
+    _assert_same(ref, _run(args))
+    monkeypatch.delenv("M3S_REFINE_INPLACE")
+    _assert_same(ref, _run(args))
+
+
 @pytest.mark.parametrize("max_iter", [0, 1])
 def test_lm_iteration_edge_cases(monkeypatch, max_iter):
     """max_iter 0: the occlusion pixel is the clamped start; 1: the LAST-only iteration."""
