@@ -445,7 +445,8 @@ __device__ __forceinline__ f2 g2fma(f2 a, f2 b, f2 c) { return __builtin_element
 // accumulate one whitened row (tracker.py:156-166): robust = si*sqrt(huber(si*r)); A = robust*J; b = robust*r.
 // MASK: the row's structurally nonzero Jacobian entries (bit c; the calib rows of chain_row2 have constant
 // -0 entries): their products add an exact +-0 to the sums and are skipped (a non-finite row still turns the
-// structurally nonzero entries into NaN, so a failing solve still fails).
+// structurally nonzero entries into NaN, so a failing solve still fails). The scale entry J[6] of a ray or pixel
+// row is zero in exact arithmetic only; it is masked as well (gn_pair).
 template <unsigned MASK = 0x7fu>
 __device__ __forceinline__ void acc_row2(f2* acc, const f2 J[7], f2 r, f2 si, float k) {
   const f2 wr = si * r;
@@ -506,7 +507,10 @@ __device__ __forceinline__ void gn_pair(const TrackParams& p, const float* T, fl
       for (int m = 0; m < 3; m++) dh[m] = di * ((k == m ? 1.0f : 0.0f) - di2 * (Y[k] * Y[m]));
       f2 J[7];
       chain_row2(dh, Y, J);
-      acc_row2(acc, J, res[k], si_r, p.huber_k);
+      // J[6] = -(dh . Y) is zero: a point's ray does not change with its length. Its fp32 value is rounding noise
+      // (~1e-7) that the ray rows' weight, 1e7 times the distance row's (sigma_dist / sigma_ray squared), adds to
+      // the scale's gradient, which only the distance rows determine: at N = 63 it moved the scale by 2.3e-5
+      acc_row2<0b0111111u>(acc, J, res[k], si_r, p.huber_k);
     }
     f2 J[7];
     chain_row2(rr, Y, J);
@@ -532,12 +536,13 @@ __device__ __forceinline__ void gn_pair(const TrackParams& p, const float* T, fl
     dh[1] = z2;
     dh[2] = (-p.K[0] * x * zi) * zi;
     chain_row2(dh, Y, J);
-    acc_row2<0b1111101u>(acc, J, res[0], si_p, p.huber_k);
+    // the pixel rows' J[6] = -(dh . Y) is zero too (a projection does not change with the point's scale)
+    acc_row2<0b0111101u>(acc, J, res[0], si_p, p.huber_k);
     dh[0] = z2;
     dh[1] = p.K[4] * zi;
     dh[2] = (-p.K[4] * y * zi) * zi;
     chain_row2(dh, Y, J);
-    acc_row2<0b1111110u>(acc, J, res[1], si_p, p.huber_k);
+    acc_row2<0b0111110u>(acc, J, res[1], si_p, p.huber_k);
     dh[0] = z2;
     dh[1] = z2;
     dh[2] = zi;

@@ -403,14 +403,21 @@ def _huber_w(r, k):
     return np.where(ra < k, 1.0, k / np.maximum(ra, 1e-300))
 
 
-def _solve(sqrt_info, r, J, k):
-    """tracker.py:156-171 in fp64."""
+def _solve(sqrt_info, r, J, k, stats=None):
+    """tracker.py:156-171 in fp64. ``stats`` (a dict) receives the cost and, among the whitened rows with non-zero
+    weight, how many have Huber active (|sqrt_info r| >= k) and inactive, and the normal equations H, g; filled before
+    the factorisation."""
     robust = sqrt_info * np.sqrt(_huber_w(sqrt_info * r, k))
     A = (robust[..., None] * J).reshape(-1, 7)
     b = (robust * r).reshape(-1, 1)
     H = A.T @ A
     g = -A.T @ b
     cost = 0.5 * float((b.T @ b)[0, 0])
+    if stats is not None:
+        live = sqrt_info != 0
+        active = np.abs(sqrt_info * r) >= k
+        stats.update(cost=cost, huber_active=int((live & active).sum()), huber_inactive=int((live & ~active).sum()),
+                     H=H, g=g.reshape(-1))
     L = np.linalg.cholesky(H)
     tau = np.linalg.solve(L.T, np.linalg.solve(L, g)).reshape(-1)
     return tau, cost
@@ -431,8 +438,11 @@ def _act_jac(T, X):
 
 
 def track_rays(Xf, Xk, T_WCf, T_WCk, Qk, valid, sigma_ray=0.003, sigma_dist=10.0, huber_k=1.345,
-               max_iters=50, rel_error=1e-3, delta_norm=1e-3, fixed_iters=None):
-    """tracker.py:173-214 (opt_pose_ray_dist_sim3) in fp64. Returns (T_WCf, T_CkCf, iters)."""
+               max_iters=50, rel_error=1e-3, delta_norm=1e-3, fixed_iters=None, trace=None):
+    """tracker.py:173-214 (opt_pose_ray_dist_sim3) in fp64. Returns (T_WCf, T_CkCf, iters). ``trace`` (a list)
+    receives one dict per GN step, linearised at the pose the step started from: cost, tau_norm, rel (the relative
+    cost change of the convergence test; nan on the first step), huber_active / huber_inactive (_solve) and the number
+    of points with valid false (n_invalid)."""
     Xf, Xk = Xf.astype(np.float64), Xk.astype(np.float64)
     v = valid.reshape(-1, 1).astype(np.float64)
     sq = np.sqrt(Qk.reshape(-1, 1).astype(np.float64))
@@ -453,11 +463,17 @@ def track_rays(Xf, Xk, T_WCf, T_WCk, Qk, valid, sigma_ray=0.003, sigma_dist=10.0
         drd = np.concatenate((dr, r_[:, None, :]), 1)
         r = rd_k - rd
         J = -drd @ dY
-        tau, cost = _solve(sqrt_info, r, J, huber_k)
+        stats = None if trace is None else {"n_invalid": int((v == 0).sum())}
+        if trace is not None:
+            trace.append(stats)
+        tau, cost = _solve(sqrt_info, r, J, huber_k, stats)
         T = sim3_retr(T, tau)
         it = step + 1
-        if fixed_iters is None:
+        if fixed_iters is None or trace is not None:
             rel = abs((old - cost) / old) if np.isfinite(old) else np.nan
+        if trace is not None:
+            stats.update(tau_norm=float(np.linalg.norm(tau)), rel=float(rel))
+        if fixed_iters is None:
             if rel < rel_error or np.linalg.norm(tau) < delta_norm:
                 break
         old = cost
@@ -466,8 +482,10 @@ def track_rays(Xf, Xk, T_WCf, T_WCk, Qk, valid, sigma_ray=0.003, sigma_dist=10.0
 
 def track_calib(Xf, Xk, T_WCf, T_WCk, Qk, valid, meas_k, valid_meas_k, K, img_size, sigma_pixel=1.0,
                 sigma_depth=10.0, huber_k=1.345, pixel_border=-10, depth_eps=1e-6, max_iters=50,
-                rel_error=1e-3, delta_norm=1e-3, fixed_iters=None):
-    """tracker.py:216-266 (opt_pose_calib_sim3) + geometry.project_calib in fp64."""
+                rel_error=1e-3, delta_norm=1e-3, fixed_iters=None, trace=None):
+    """tracker.py:216-266 (opt_pose_calib_sim3) + geometry.project_calib in fp64. ``trace``: as in track_rays, plus
+    the number of points failing z > depth_eps (n_behind), failing the border test with z > depth_eps (n_border),
+    with valid_meas false (n_invalid_meas) and with valid false (n_invalid)."""
     Xf = Xf.astype(np.float64)
     v = valid.reshape(-1, 1).astype(np.float64)
     sq = np.sqrt(Qk.reshape(-1, 1).astype(np.float64))
@@ -501,11 +519,19 @@ def track_calib(Xf, Xk, T_WCf, T_WCk, Qk, valid, meas_k, valid_meas_k, K, img_si
         si2 = (valid_p & vm) * sqrt_info
         r = meas_k - pz
         J = -dpz @ dY
-        tau, cost = _solve(si2, r, J, huber_k)
+        stats = None if trace is None else {
+            "n_behind": int((~valid_z).sum()), "n_border": int((valid_z & ~valid_p).sum()),
+            "n_invalid_meas": int((~vm.astype(bool)).sum()), "n_invalid": int((v == 0).sum())}
+        if trace is not None:
+            trace.append(stats)
+        tau, cost = _solve(si2, r, J, huber_k, stats)
         T = sim3_retr(T, tau)
         it = step + 1
-        if fixed_iters is None:
+        if fixed_iters is None or trace is not None:
             rel = abs((old - cost) / old) if np.isfinite(old) else np.nan
+        if trace is not None:
+            stats.update(tau_norm=float(np.linalg.norm(tau)), rel=float(rel))
+        if fixed_iters is None:
             if rel < rel_error or np.linalg.norm(tau) < delta_norm:
                 break
         old = cost
