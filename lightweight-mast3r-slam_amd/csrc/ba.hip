@@ -123,20 +123,20 @@ __device__ __forceinline__ void pair_flush(double* acc, const f2* fL, const f2* 
   }
 }
 
-// Per-call point records (once per gauss_newton call; the GN iterations only move the poses):
-//   rec[e][k] = {Xi (points / rays) ; sw} (16 B) or, calib, {u_t | v_t << 16, log z_i | NaN if z_i <= z_eps, sw}
-//   (12 B: the lin kernel streams E x N records every iteration, so a quarter less HBM traffic) with
-//   Xi = Xs[i][valid ? idx : 0]
-//   (gn_kernels.cu reads index 0 for an invalid match) and sw = sqrt(q) when the match is valid and
-//   q > Q_thresh, c_i > C_thresh, c_j > C_thresh, else 0 (gn_kernels.cu:880-906) — the per-iteration
-//   gathers, int64 index loads and threshold tests leave the linearisation loop.
-// Only the edges of a.pack_list when the plan reuses records (m3s_ba_make_plan_reuse: the rest kept theirs), each
-// into its record slot.
-// the record of point k of shard edge e (ix, jx: its pose ranks); rays: *n = |Xi| (the record holds Xi / |Xi|,
-// computed with the linearisation's own instruction sequence, so the rows are bit-identical to normalising there)
 // the pack's per-edge streams (valid, idx, Q, C_j) are read once per call: non-temporal
 #define BA_NT_LOAD(ptr) __builtin_nontemporal_load(ptr)
-// the record of a matched point from its gathered X_i (ind: its pixel in keyframe i) and its folded validity
+// The per-call point records, built once per gauss_newton call (the GN iterations only move the poses), so that the
+// per-iteration gathers, int64 index loads and threshold tests leave the linearisation loop. The record of point k of
+// shard edge e, rec[e][k], with Xi = Xs[i][valid ? idx : 0] (gn_kernels.cu reads index 0 for an invalid match):
+//   points  {Xi ; sw}                                               16 B
+//   rays    {Xi / |Xi| ; sw}, |Xi| in the slot's second array       16 B + 4 B (computed with the linearisation's own
+//           instruction sequence, so the rows are bit-identical to normalising there)
+//   calib   {u_t | v_t << 16, log z_i (NaN if z_i <= z_eps), sw}    12 B (the lin kernel streams E x N records every
+//           iteration: a quarter less HBM traffic)
+// sw = sqrt(q) when the match is valid and q > Q_thresh, c_i > C_thresh, c_j > C_thresh, else 0 (gn_kernels.cu:880-906)
+// When the plan reuses records (m3s_ba_make_plan_reuse) only the edges of a.pack_list are packed, each into its slot.
+// the record of a matched point from its gathered X_i (ind: its pixel in keyframe i) and its folded validity;
+// rays: *n = |Xi|
 template <int MODE>
 __device__ __forceinline__ float4 pack_finish(const BaParams& p, const float* Xi, int64_t ind, float q, bool valid,
                                               float* n) {
@@ -318,99 +318,192 @@ __global__ void __launch_bounds__(256) ba_kf_compare_kernel(const BaKfCopy* __re
   if (__any(diff) && (threadIdx.x & 63) == 0) dirty[k] = 1;
 }
 
-// raw calib: LDS room for the plan's pixel-ray tables (x_of_u then y_of_v); only the raw-calib instances allocate it
-#ifndef BA_RAY_LDS
-#define BA_RAY_LDS 2048  // floats: 8 KB on top of the 38 KB of the flush, three blocks per CU still fit its 160 KB
-#endif
-template <bool ON>
-__device__ __forceinline__ float* ray_lds() {
-  if constexpr (ON) {
-    __shared__ float s_ray[BA_RAY_LDS];
-    return s_ray;
-  } else {
-    return nullptr;
-  }
+// ba_lin_kernel's parts ----------------------------------------------------------------------
+__device__ __forceinline__ float uniform_f(float x) {  // a block-uniform value, pinned in an SGPR
+  return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, x)));
 }
-
-// PACK: the first GN iteration of a call that packs every edge builds each point's record itself (pack_record, the
-// same values) and stores it for the later iterations: the pack's gathers (HBM-bound) run under this kernel's
-// VALU-bound rows instead of as a separate launch before it.
-// RAYLDS (raw calib only): the pixel-ray tables fit BA_RAY_LDS and are read from LDS (else through the cache)
-template <int MODE, bool PACK, bool RAYLDS = false>  // specialised per residual type: one mode's registers, not the union of three
-__global__ void __launch_bounds__(256, BA_LIN_WAVES) ba_lin_kernel(BaArgs a, BaParams p) {
-  if (*a.done) return;
-  // the plan's block table: edges grouped by target keyframe, consecutive blocks on one XCD (xcd_remap)
-  const int code = a.lin_tab[xcd_remap(blockIdx.x, gridDim.x)];
-  const int e = code / p.chunks;
-  const int chunk = code - e * p.chunks;
-  const int N = p.N;
-  const int ix = a.ii_rank[e], jx = a.jj_rank[e];
-  float Ti[8], Tj[8], Tij[8];
-#pragma unroll
-  for (int c = 0; c < 8; c++) {
-    Ti[c] = a.Twc[ix * 8 + c];
-    Tj[c] = a.Twc[jx * 8 + c];
-  }
-  // T_ij in double (relSim3_d): in fp32 its translation t_j - t_i rounds at |t_i| (metres), an error coherent over
-  // every point of the edge (C4 EuRoC graph: 2.6e-6 -> 5e-7 from the fp64 truth, scripts/ba_prec_exp.py)
-  double Td[8];
-  relSim3_d(Ti, Tj, Td);
-#pragma unroll
-  for (int c = 0; c < 8; c++) Tij[c] = (float)Td[c];
-  // the linear map of actSO3 (Y = X + 2w q x X + 2 q x (q x X), any |q|) times s, formed in fp64 once per block:
-  // s (I + 2w[q]x + 2([q][q]^T - |q|^2 I)), kept as its difference from the identity, D = s R - I (Y = X + (D X + t)):
-  // D is small for the near-identity relative poses of co-visible keyframes, so rounding it to fp32 costs far less
-  // than rounding s R itself (which put the ill-conditioned 6-KF fixtures at 1.6-1.8e-5 from the fp64 truth)
-  float M[9];
-  {
+// The block-uniform state of the edge between the poses of ranks ix and jx: T_ij as the map Y = X + (D X + t) of a
+// point of keyframe j into keyframe i, D and t in SGPRs (the packed FMAs read them as scalar operands)
+struct LinEdge {
+  float D[9], t[3];  // D = s R - I, row-major
+  __device__ __forceinline__ LinEdge(const BaArgs& a, int ix, int jx) {
+    // T_ij in double (relSim3_d): in fp32 its translation t_j - t_i rounds at |t_i| (metres), an error coherent over
+    // every point of the edge (C4 EuRoC graph: 2.6e-6 -> 5e-7 from the fp64 truth, scripts/ba_prec_exp.py)
+    double Td[8];
+    relSim3_d(a.Twc + ix * 8, a.Twc + jx * 8, Td);
+    // the linear map of actSO3 (Y = X + 2w q x X + 2 q x (q x X), any |q|) times s, in fp64 once per block, kept as its
+    // difference from the identity, D = s R - I: small for the near-identity relative poses of co-visible keyframes, so
+    // rounding it to fp32 costs far less than rounding s R (ill-conditioned 6-KF fixtures: 1.6-1.8e-5 from the truth)
     const double x = Td[3], y = Td[4], z = Td[5], w = Td[6], sc = Td[7];
     const double R[9] = {1.0 - 2.0 * (y * y + z * z), 2.0 * (x * y - z * w),       2.0 * (x * z + y * w),
                          2.0 * (x * y + z * w),       1.0 - 2.0 * (x * x + z * z), 2.0 * (y * z - x * w),
                          2.0 * (x * z - y * w),       2.0 * (y * z + x * w),       1.0 - 2.0 * (x * x + y * y)};
 #pragma unroll
-    for (int c = 0; c < 9; c++) {  // block-uniform: kept in SGPRs (the packed FMAs read them as scalar operands)
-      const double d = sc * R[c] - ((c % 4 == 0) ? 1.0 : 0.0);
-      M[c] = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, (float)d)));
-    }
+    for (int c = 0; c < 9; c++) D[c] = uniform_f((float)(sc * R[c] - ((c % 4 == 0) ? 1.0 : 0.0)));
+#pragma unroll
+    for (int c = 0; c < 3; c++) t[c] = uniform_f((float)Td[c]);
+  }
+  // actSim3 (gn_kernels.cu:207-219) as the edge's map X + (D X + t): three packed FMAs and an add per component
+  __device__ __forceinline__ void act(const f2 Xj[3], f2 Y[3]) const {
 #pragma unroll
     for (int c = 0; c < 3; c++)
-      Tij[c] = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, Tij[c])));
+      Y[c] = Xj[c] + __builtin_elementwise_fma(
+                         f2{D[3 * c], D[3 * c]}, Xj[0],
+                         __builtin_elementwise_fma(f2{D[3 * c + 1], D[3 * c + 1]}, Xj[1],
+                                                   __builtin_elementwise_fma(f2{D[3 * c + 2], D[3 * c + 2]}, Xj[2],
+                                                                             f2{t[c], t[c]})));
   }
-  // the block's fp64 sums: a flush transposes the lanes' fp64 pair sums through LDS (s_fl: conflict-free, one
-  // column per thread) and 7 threads per sum add its 128 lanes, then the 7 partials in order: ~40 instructions per
-  // thread instead of a 6-level fp64 shuffle butterfly per sum (~110 VALU per sum and wave, ~15 % of the kernel)
-  __shared__ double s_fl[BA_PAIR_HALF][256];
-  __shared__ double s_red[35][7];
-  __shared__ double s_tot[BA_NSUM];
-  if (threadIdx.x < BA_NSUM) s_tot[threadIdx.x] = 0.0;
-  float4* rec = rec_of_slot(a, a.rec_slot ? a.rec_slot[e] : e, N);
-  float* rec_n = reinterpret_cast<float*>(rec + N);  // rays: |Xi|
-  const float* Xj_base = a.Xkf[jx];
-  const int per = (N + p.chunks - 1) / p.chunks;
-  const int k_begin = chunk * per;
-  const int k_end = min(N, k_begin + per);
-  // raw calib: X_j = (z_j x_of_u[u], z_j y_of_v[v], z_j) from the raw point's depth and the plan's ray tables (the
-  // values of constrain_points_to_ray: one rounded product per component, z_j * 1 exact). (pu, pv) is the pixel of this
-  // lane's first point of the coming round, k00 + threadIdx.x: one division per lane here, then a round adds the
-  // block-uniform (su, sv) = (stride % W, stride / W) with one wrap test; the second point sits (hu, hv) further.
-  // pix_next hands out the table entries of the round's two points and steps to the next round; it is called once per
-  // round, in round order. A lane past the chunk's end (its rows are skipped) may walk past the last image row: its v
-  // is clamped so that the table loads stay inside the tables.
-  // z_j is loaded through a global-memory pointer: a pointer read from the keyframe table is generic to the compiler,
-  // and a flat load counts against the LDS / scalar-memory counter too, which returns out of order: the wait for this
-  // round's z_j then also waited for the next round's prefetch issued just before it (the whole latency, every round)
-  typedef const float __attribute__((address_space(1))) * gfloat_p;
-  const gfloat_p Zj_base = (gfloat_p)(Xj_base + 2);
-  // RAYLDS: the block first copies the tables into LDS (the launcher picks this instance when W + H <= BA_RAY_LDS
-  // floats: every configured size): the per-round look-ups are then LDS reads, which leave the vector-memory pipe to
-  // the record and z_j streams; larger images read the tables through the cache.
-  int pu = 0, pv = 0, su = 0, sv = 0, hu = 0, hv = 0;
-  float* const s_ray = ray_lds<RAYLDS>();
-  if constexpr (MODE == BA_MODE_CALIB_RAW) {
-    const int W = p.W, kk = k_begin + (int)threadIdx.x, half = (int)blockDim.x;
+};
+struct RunSums {  // a lane's fp32 run sums, one slot per point of its pair
+  f2 L[28], v[7];
+  __device__ __forceinline__ void clear() { *this = RunSums{}; }
+};
+// the block's fp64 sums (tot) and the room a flush transposes through; each array 16-B aligned, as LDS arrays are
+struct LinLds {
+  alignas(16) double fl[BA_PAIR_HALF][256];
+  alignas(16) double red[35][7];
+  alignas(16) double tot[BA_NSUM];
+};
+
+// A run's fp32 sums into the block's fp64 sums, and the run sums cleared: the lanes of a pair trade the halves they
+// own (pair_flush: fp64 adds from 0 in a per-lane accumulator's order), then the pair sums are transposed through LDS
+// (fl: conflict-free, one column per thread), 7 threads per sum add its 128 lanes and then the 7 partials in order: ~40
+// instructions per thread, not a 6-level fp64 shuffle butterfly per sum (~110 VALU per sum and wave, ~15 % of the
+// kernel). A chunk is at most BA_RUN_LEN rounds (ba_chunks): this runs once per block and no fp64 accumulator is live
+// across the point loop: its VGPRs carry the next round's prefetched records. Block-uniform (barriers, and the pair
+// flush swaps between lanes): every thread of the block must reach every flush.
+__device__ __forceinline__ void lin_flush(RunSums& s, LinLds& lds) {
+  const int t = threadIdx.x;
+  double acc[BA_PAIR_HALF] = {};
+  pair_flush(acc, s.L, s.v, t & 1);
+#pragma unroll
+  for (int m = 0; m < BA_PAIR_HALF; m++) lds.fl[m][t] = acc[m];
+  __syncthreads();
+  if (t < 35 * 7) {  // sum c: even lanes own 0..17, odd lanes 18..34
+    const int c = t / 7, part = t - 7 * c;
+    const int par = c >= BA_PAIR_HALF ? 1 : 0, m = c - BA_PAIR_HALF * par;
+    double r = 0.0;
+    for (int i = part; i < 128; i += 7) r += lds.fl[m][2 * i + par];
+    lds.red[c][part] = r;
+  }
+  __syncthreads();
+  if (t < 35) {
+    double r = lds.tot[t];
+#pragma unroll
+    for (int q = 0; q < 7; q++) r += lds.red[t][q];
+    lds.tot[t] = r;
+  }
+  s.clear();
+}
+
+// The rows of one round, one function per residual model: two points per lane, every per-point float operation on both
+// at once as one packed fp32 instruction (v_pk_fma/mul/add_f32; float2 lanes), the transcendentals per component. Y:
+// points of keyframe j in keyframe i (LinEdge::act); Rx, Ry, Rz: the records' fields as computed on; sqq: sqrt(q) or 0
+__device__ __forceinline__ void rows_points(const BaParams& p, const f2 Y[3], f2 Rx, f2 Ry, f2 Rz, f2 sqq, RunSums& s) {
+  const f2 err[3] = {Y[0] - Rx, Y[1] - Ry, Y[2] - Rz};
+  const f2 sw = p.inv_a * sqq, wc = sw * sw;
+  const f2 z2 = {0.0f, 0.0f}, o2 = {1.0f, 1.0f};
+  const f2 J0[7] = {o2, z2, z2, z2, Y[2], -Y[1], Y[0]};
+  const f2 J1[7] = {z2, o2, z2, -Y[2], z2, Y[0], Y[1]};
+  const f2 J2[7] = {z2, z2, o2, Y[1], -Y[0], z2, Y[2]};
+  acc_local_f2<0b1110001>(s.L, s.v, J0, huber_ba2(sw * err[0]) * wc, err[0]);  // {0,4,5,6}
+  acc_local_f2<0b1101010>(s.L, s.v, J1, huber_ba2(sw * err[1]) * wc, err[1]);  // {1,3,5,6}
+  acc_local_f2<0b1011100>(s.L, s.v, J2, huber_ba2(sw * err[2]) * wc, err[2]);  // {2,3,4,6}
+}
+// (Rx, Ry, Rz) = ri = Xi / |Xi| and n1i = |Xi| (pack_finish: the same operations, once per call)
+__device__ __forceinline__ void rows_rays(const BaParams& p, const f2 Y[3], f2 Rx, f2 Ry, f2 Rz, f2 n1i, f2 sqq,
+                                          RunSums& s) {
+  const f2 n2j = Y[0] * Y[0] + Y[1] * Y[1] + Y[2] * Y[2];
+  const f2 n1j_inv = rsq2(n2j);
+  const f2 n1j = n2j * n1j_inv;
+  const f2 rj[3] = {n1j_inv * Y[0], n1j_inv * Y[1], n1j_inv * Y[2]};
+  const f2 err[4] = {rj[0] - Rx, rj[1] - Ry, rj[2] - Rz, n1j - n1i};
+  const f2 swr = p.inv_a * sqq, swd = p.inv_b * sqq;
+  const f2 wr = swr * swr, wd = swd * swd;
+  const f2 n3 = n1j_inv * rcp2(n2j);
+  const f2 dxx = n1j_inv - Y[0] * Y[0] * n3, dyy = n1j_inv - Y[1] * Y[1] * n3, dzz = n1j_inv - Y[2] * Y[2] * n3;
+  const f2 dxy = -Y[0] * Y[1] * n3, dxz = -Y[0] * Y[2] * n3, dyz = -Y[1] * Y[2] * n3;
+  const f2 z2 = {0.0f, 0.0f};
+  const f2 J0[7] = {dxx, dxy, dxz, z2, rj[2], -rj[1], z2};
+  const f2 J1[7] = {dxy, dyy, dyz, -rj[2], z2, rj[0], z2};
+  const f2 J2[7] = {dxz, dyz, dzz, rj[1], -rj[0], z2, z2};
+  const f2 J3[7] = {rj[0], rj[1], rj[2], z2, z2, z2, n1j};
+  acc_local_f2<0b0110111>(s.L, s.v, J0, huber_ba2(swr * err[0]) * wr, err[0]);  // {0,1,2,4,5}
+  acc_local_f2<0b0101111>(s.L, s.v, J1, huber_ba2(swr * err[1]) * wr, err[1]);  // {0,1,2,3,5}
+  acc_local_f2<0b0011111>(s.L, s.v, J2, huber_ba2(swr * err[2]) * wr, err[2]);  // {0,1,2,3,4}
+  acc_local_f2<0b1000111>(s.L, s.v, J3, huber_ba2(swd * err[3]) * wd, err[3]);  // {0,1,2,6}
+}
+// both calib modes; lzi: log z_i, NaN where z_i <= z_eps (pack_finish)
+__device__ __forceinline__ void rows_calib(const BaParams& p, const f2 Y[3], f2 u_t, f2 v_t, f2 lzi, f2 sqq,
+                                           RunSums& s) {
+  const auto valid_z = (Y[2] > p.z_eps) & (lzi == lzi);
+  const f2 z2 = {0.0f, 0.0f};
+  const f2 zj_inv = valid_z ? f2{__builtin_amdgcn_rcpf(Y[2].x), __builtin_amdgcn_rcpf(Y[2].y)} : z2;
+  const f2 zj_log = valid_z ? f2{__logf(Y[2].x), __logf(Y[2].y)} : z2;
+  const f2 zi_log = valid_z ? lzi : z2;
+  const f2 xz = Y[0] * zj_inv, yz = Y[1] * zj_inv;
+  const f2 u = __builtin_elementwise_fma(f2{p.fx, p.fx}, xz, f2{p.cx, p.cx}),
+           vv = __builtin_elementwise_fma(f2{p.fy, p.fy}, yz, f2{p.cy, p.cy});
+  const float ub = (float)p.pixel_border, uh = (float)(p.W - 1 - p.pixel_border),
+              vh = (float)(p.H - 1 - p.pixel_border);
+  const auto valid = (u > ub) & (u < uh) & (vv > ub) & (vv < vh) & valid_z;
+  const f2 err[3] = {u - u_t, vv - v_t, zj_log - zi_log};
+  const f2 swp = valid ? p.inv_a * sqq : z2;
+  const f2 swd = valid ? p.inv_b * sqq : z2;
+  const f2 wp = swp * swp, wd = swd * swd;
+  const float fx = p.fx, fy = p.fy;
+  const f2 o2 = {1.0f, 1.0f};
+  const f2 J0[7] = {fx * zj_inv, z2, -fx * xz * zj_inv, -fx * xz * yz, fx * __builtin_elementwise_fma(xz, xz, o2),
+                    -fx * yz, z2};
+  const f2 J1[7] = {z2, fy * zj_inv, -fy * yz * zj_inv, -fy * __builtin_elementwise_fma(yz, yz, o2), fy * xz * yz,
+                    fy * xz, z2};
+  const f2 J2[7] = {z2, z2, zj_inv, yz, -xz, z2, o2};
+  acc_local_f2<0b0111101>(s.L, s.v, J0, huber_ba2(swp * err[0]) * wp, err[0]);  // {0,2,3,4,5}
+  acc_local_f2<0b0111110>(s.L, s.v, J1, huber_ba2(swp * err[1]) * wp, err[1]);  // {1,2,3,4,5}
+  acc_local_f2<0b1011100>(s.L, s.v, J2, huber_ba2(swd * err[2]) * wd, err[2]);  // {2,3,4,6}
+}
+// the part the models share. R0, R1: the records as computed on (rec_expand); a missing second point (!has1) is the
+// first again with weight 0: exact zeros unless the first's own row is non-finite, which poisons the sums anyway
+// (another point as filler changed the rays sums)
+template <int MODE>
+__device__ __forceinline__ void rows(const BaParams& p, const LinEdge& edge, const float4& R0, const float4& R1,
+                                     f2 nI, const f2 Xj[3], bool has1, RunSums& s) {
+  const f2 Rx = {R0.x, R1.x}, Ry = {R0.y, R1.y}, Rz = {R0.z, R1.z};
+  // sqrt(q), 0 for an invalid match (ba_pack) and for the missing second point of a ragged tail
+  const f2 sqq = {R0.w, has1 ? R1.w : 0.0f};
+  f2 Y[3];
+  edge.act(Xj, Y);
+  if constexpr (MODE == BA_MODE_POINTS) rows_points(p, Y, Rx, Ry, Rz, sqq, s);
+  else if constexpr (MODE == BA_MODE_RAYS) rows_rays(p, Y, Rx, Ry, Rz, nI, sqq, s);
+  else rows_calib(p, Y, Rx, Ry, Rz, sqq, s);
+}
+// raw calib: LDS room for the plan's pixel-ray tables (x_of_u then y_of_v); only the raw-calib instances allocate it
+#ifndef BA_RAY_LDS
+#define BA_RAY_LDS 2048  // floats: 8 KB on top of the 38 KB of the flush, three blocks per CU still fit its 160 KB
+#endif
+// Raw calib: the pixels of a lane's two points, round by round. X_j = (z_j x_of_u[u], z_j y_of_v[v], z_j) from the raw
+// point's depth and the plan's ray tables (constrain_points_to_ray's values: one rounded product per component, z_j * 1
+// exact). (pu, pv): the pixel of the lane's first point of the coming round, one division per lane in init; a round
+// adds the block-uniform (su, sv) = (stride % W, stride / W) with one wrap test; the second point is (hu, hv) further.
+// Contract: init once, by every thread of the block (RAYLDS: a barrier), then next once per round, in round order from
+// the round at k_begin. A lane past the chunk's end (its rows are skipped) may walk past the last image row: its v is
+// clamped so that the loads stay inside the tables. RAYLDS: init first copies the tables into LDS (the launcher picks
+// this instance when W + H <= BA_RAY_LDS floats: every configured size), the look-ups are then LDS reads, which leave
+// the vector-memory pipe to the record and z_j streams; larger images read through the cache.
+template <bool RAYLDS>
+struct PixWalk {
+  int pu = 0, pv = 0, su = 0, sv = 0, hu = 0, hv = 0, W = 0, vmax = 0;
+  const float* tab = nullptr;  // x_of_u (W floats) then y_of_v (H floats)
+  __device__ __forceinline__ void init(const BaArgs& a, const BaParams& p, int k_begin) {
+    const int kk = k_begin + (int)threadIdx.x, half = (int)blockDim.x;
+    W = p.W;
+    vmax = p.H - 1;
+    tab = a.ray_tab;
     if constexpr (RAYLDS) {
+      __shared__ float s_ray[BA_RAY_LDS];
       for (int i = (int)threadIdx.x; i < W + p.H; i += half) s_ray[i] = a.ray_tab[i];
       __syncthreads();
+      tab = s_ray;
     }
     pv = kk / W;
     pu = kk - pv * W;
@@ -419,243 +512,160 @@ __global__ void __launch_bounds__(256, BA_LIN_WAVES) ba_lin_kernel(BaArgs a, BaP
     sv = (2 * half) / W;
     su = 2 * half - sv * W;
   }
-  auto pix_next = [&](bool has1, f2& xu, f2& yv) {
-    const int W = p.W, vmax = p.H - 1;
+  // the table entries of the round's two points (a missing second point repeats the first, as in rows), then the step
+  __device__ __forceinline__ void next(bool has1, f2& xu, f2& yv) {
     int u1 = pu + hu, v1 = pv + hv;
     if (u1 >= W) {
       u1 -= W;
       v1++;
     }
-    if (!has1) {  // the missing second point repeats the first (rows)
+    if (!has1) {
       u1 = pu;
       v1 = pv;
     }
-    const int i0 = W + min(pv, vmax), i1 = W + min(v1, vmax);
-    if constexpr (RAYLDS) {
-      xu = f2{s_ray[pu], s_ray[u1]};
-      yv = f2{s_ray[i0], s_ray[i1]};
-    } else {
-      xu = f2{a.ray_tab[pu], a.ray_tab[u1]};
-      yv = f2{a.ray_tab[i0], a.ray_tab[i1]};
-    }
+    xu = f2{tab[pu], tab[u1]};
+    yv = f2{tab[W + min(pv, vmax)], tab[W + min(v1, vmax)]};
     pu += su;
     pv += sv;
     if (pu >= W) {
       pu -= W;
       pv++;
     }
-  };
-  f2 fL[28], fv[7];  // fp32 run sums, one slot per point of the pair
+  }
+};
+// z_j is loaded through a global-memory pointer: a pointer read from the keyframe table is generic to the compiler,
+// and a flat load counts against the LDS / scalar-memory counter too, which returns out of order: the wait for this
+// round's z_j then also waited for the next round's prefetch issued just before it (the whole latency, every round)
+typedef const float __attribute__((address_space(1))) * gfloat_p;
+struct LinChunk {        // what a block streams:
+  float4* rec;           // its edge's record slot
+  float* rec_n;          // rays: |Xi|, behind the records
+  const float* Xj_base;  // the target keyframe's points
+  gfloat_p Zj_base;      // raw calib: their z alone
+  int k_begin, k_end;    // its chunk of them
+};
+// A lane's two points of the round that starts at k00, k00 + threadIdx.x and blockDim.x further. live: the first exists
+// (else the lane skips the rows); has1: so does the second. k0, k1: where the lane loads, always inside the chunk
+// (a dead lane at k_begin, a missing second point at the first again)
+struct RoundPts {
+  int k0, k1;
+  bool live, has1;
+  __device__ __forceinline__ RoundPts(const LinChunk& c, int k00) {
+    const int k = k00 + (int)threadIdx.x, bd = (int)blockDim.x;
+    live = k < c.k_end;
+    has1 = k + bd < c.k_end;
+    k0 = live ? k : c.k_begin;
+    k1 = k0 + bd < c.k_end ? k0 + bd : k0;
+  }
+};
+struct Round {    // what a lane holds of one round before its rows
+  float4 R0, R1;  // the records as stored
+  f2 nI;          // rays: |Xi| of both points
+  f2 Xj[3];       // raw calib: {x_of_u[u], y_of_v[v], z_j}, multiplied out in lin_round
+};
+template <int MODE>  // X_j of the round's points; raw calib: z_j alone (Xj[0], Xj[1] come from PixWalk::next)
+__device__ __forceinline__ void round_xj(const LinChunk& c, const RoundPts& pt, Round& r) {
+  if constexpr (MODE == BA_MODE_CALIB_RAW) {
+    r.Xj[2] = f2{c.Zj_base[(size_t)pt.k0 * 3], c.Zj_base[(size_t)pt.k1 * 3]};
+  } else {
 #pragma unroll
-  for (int c = 0; c < 28; c++) fL[c] = f2{0.0f, 0.0f};
-#pragma unroll
-  for (int c = 0; c < 7; c++) fv[c] = f2{0.0f, 0.0f};
-  // a run's fp32 sums into the block's fp64 sums: the lanes of a pair trade the halves they own (pair_flush: fp64
-  // adds from 0 in the order a per-lane accumulator would make them), then the LDS transpose above. A chunk is at
-  // most BA_RUN_LEN rounds (ba_chunks), so this runs once per block and no fp64 accumulator is live across the point
-  // loop: its VGPRs carry the next round's prefetched records instead. Block-uniform (barriers): every thread of
-  // the block reaches every flush (the trip count is the block's).
-  auto flush = [&]() {
-    const int t = threadIdx.x;
-    const bool odd = t & 1;
-    double acc[BA_PAIR_HALF];
-#pragma unroll
-    for (int m = 0; m < BA_PAIR_HALF; m++) acc[m] = 0.0;
-    pair_flush(acc, fL, fv, odd);
-#pragma unroll
-    for (int m = 0; m < BA_PAIR_HALF; m++) s_fl[m][t] = acc[m];
-    __syncthreads();
-    if (t < 35 * 7) {  // sum c: even lanes own 0..17, odd lanes 18..34
-      const int c = t / 7, part = t - 7 * c;
-      const int par = c >= BA_PAIR_HALF ? 1 : 0, m = c - BA_PAIR_HALF * par;
-      double r = 0.0;
-      for (int i = part; i < 128; i += 7) r += s_fl[m][2 * i + par];
-      s_red[c][part] = r;
-    }
-    __syncthreads();
-    if (t < 35) {
-      double r = s_tot[t];
-#pragma unroll
-      for (int q = 0; q < 7; q++) r += s_red[t][q];
-      s_tot[t] = r;
-    }
-#pragma unroll
-    for (int c = 0; c < 28; c++) fL[c] = f2{0.0f, 0.0f};
-#pragma unroll
-    for (int c = 0; c < 7; c++) fv[c] = f2{0.0f, 0.0f};
-  };
-  // the rows of one round: two points per lane, (k0, k0 + blockDim): every per-point float operation runs on both at
-  // once as one packed fp32 instruction (v_pk_fma/mul/add_f32; float2 lanes), the transcendentals per component.
-  // R0, R1: the records as computed on (rec_expand); a missing second point (has1 false) repeats the first with
-  // weight 0: it adds exact zeros unless the first point's own row is non-finite, which poisons the sums anyway
-  // (another point as filler changed the rays sums)
-  auto rows = [&](const float4& R0, const float4& R1, f2 nI, const f2* Xj, bool has1) {
-    const f2 Rx = {R0.x, R1.x}, Ry = {R0.y, R1.y}, Rz = {R0.z, R1.z};
-    // sqrt(q), 0 for an invalid match (ba_pack) and for the missing second point of a ragged tail
-    const f2 sqq = {R0.w, has1 ? R1.w : 0.0f};
-    f2 Y[3];
-    // actSim3 (gn_kernels.cu:207-219) as the edge's map X + (D X + t): three packed FMAs and an add per component
-#pragma unroll
-    for (int c = 0; c < 3; c++)
-      Y[c] = Xj[c] + __builtin_elementwise_fma(
-                         f2{M[3 * c], M[3 * c]}, Xj[0],
-                         __builtin_elementwise_fma(f2{M[3 * c + 1], M[3 * c + 1]}, Xj[1],
-                                                   __builtin_elementwise_fma(f2{M[3 * c + 2], M[3 * c + 2]}, Xj[2],
-                                                                             f2{Tij[c], Tij[c]})));
-    if constexpr (MODE == BA_MODE_POINTS) {
-      const f2 err[3] = {Y[0] - Rx, Y[1] - Ry, Y[2] - Rz};
-      const f2 sw = p.inv_a * sqq;
-      const f2 wc = sw * sw;
-      const f2 z2 = {0.0f, 0.0f}, o2 = {1.0f, 1.0f};
-      const f2 J0[7] = {o2, z2, z2, z2, Y[2], -Y[1], Y[0]};
-      const f2 J1[7] = {z2, o2, z2, -Y[2], z2, Y[0], Y[1]};
-      const f2 J2[7] = {z2, z2, o2, Y[1], -Y[0], z2, Y[2]};
-      acc_local_f2<0b1110001>(fL, fv, J0, huber_ba2(sw * err[0]) * wc, err[0]);  // {0,4,5,6}
-      acc_local_f2<0b1101010>(fL, fv, J1, huber_ba2(sw * err[1]) * wc, err[1]);  // {1,3,5,6}
-      acc_local_f2<0b1011100>(fL, fv, J2, huber_ba2(sw * err[2]) * wc, err[2]);  // {2,3,4,6}
-    } else if constexpr (MODE == BA_MODE_RAYS) {
-      // the record holds ri = Xi / |Xi| and rec_n |Xi| (pack_record: the same operations, once per call)
-      const f2 n1i = nI;
-      const f2 n2j = Y[0] * Y[0] + Y[1] * Y[1] + Y[2] * Y[2];
-      const f2 n1j_inv = rsq2(n2j);
-      const f2 n1j = n2j * n1j_inv;
-      const f2 rj[3] = {n1j_inv * Y[0], n1j_inv * Y[1], n1j_inv * Y[2]};
-      const f2 err[4] = {rj[0] - Rx, rj[1] - Ry, rj[2] - Rz, n1j - n1i};
-      const f2 swr = p.inv_a * sqq;
-      const f2 swd = p.inv_b * sqq;
-      const f2 wr = swr * swr, wd = swd * swd;
-      const f2 n3 = n1j_inv * rcp2(n2j);
-      const f2 dxx = n1j_inv - Y[0] * Y[0] * n3;
-      const f2 dyy = n1j_inv - Y[1] * Y[1] * n3;
-      const f2 dzz = n1j_inv - Y[2] * Y[2] * n3;
-      const f2 dxy = -Y[0] * Y[1] * n3;
-      const f2 dxz = -Y[0] * Y[2] * n3;
-      const f2 dyz = -Y[1] * Y[2] * n3;
-      const f2 z2 = {0.0f, 0.0f};
-      const f2 J0[7] = {dxx, dxy, dxz, z2, rj[2], -rj[1], z2};
-      const f2 J1[7] = {dxy, dyy, dyz, -rj[2], z2, rj[0], z2};
-      const f2 J2[7] = {dxz, dyz, dzz, rj[1], -rj[0], z2, z2};
-      const f2 J3[7] = {rj[0], rj[1], rj[2], z2, z2, z2, n1j};
-      acc_local_f2<0b0110111>(fL, fv, J0, huber_ba2(swr * err[0]) * wr, err[0]);  // {0,1,2,4,5}
-      acc_local_f2<0b0101111>(fL, fv, J1, huber_ba2(swr * err[1]) * wr, err[1]);  // {0,1,2,3,5}
-      acc_local_f2<0b0011111>(fL, fv, J2, huber_ba2(swr * err[2]) * wr, err[2]);  // {0,1,2,3,4}
-      acc_local_f2<0b1000111>(fL, fv, J3, huber_ba2(swd * err[3]) * wd, err[3]);  // {0,1,2,6}
-    } else {  // calib
-      const f2 u_t = Rx, v_t = Ry, lzi = Rz;  // lzi: log z_i, NaN where z_i <= z_eps (pack_record)
-      const auto valid_z = (Y[2] > p.z_eps) & (lzi == lzi);
-      const f2 z2 = {0.0f, 0.0f};
-      const f2 zj_inv = valid_z ? f2{__builtin_amdgcn_rcpf(Y[2].x), __builtin_amdgcn_rcpf(Y[2].y)} : z2;
-      const f2 zj_log = valid_z ? f2{__logf(Y[2].x), __logf(Y[2].y)} : z2;
-      const f2 zi_log = valid_z ? lzi : z2;
-      const f2 xz = Y[0] * zj_inv, yz = Y[1] * zj_inv;
-      const f2 u = __builtin_elementwise_fma(f2{p.fx, p.fx}, xz, f2{p.cx, p.cx}),
-               vv = __builtin_elementwise_fma(f2{p.fy, p.fy}, yz, f2{p.cy, p.cy});
-      const float ub = (float)p.pixel_border, uh = (float)(p.W - 1 - p.pixel_border),
-                  vh = (float)(p.H - 1 - p.pixel_border);
-      const auto valid = (u > ub) & (u < uh) & (vv > ub) & (vv < vh) & valid_z;
-      const f2 err[3] = {u - u_t, vv - v_t, zj_log - zi_log};
-      const f2 swp = valid ? p.inv_a * sqq : z2;
-      const f2 swd = valid ? p.inv_b * sqq : z2;
-      const f2 wp = swp * swp, wd = swd * swd;
-      const float fx = p.fx, fy = p.fy;
-      const f2 o2 = {1.0f, 1.0f};
-      const f2 J0[7] = {fx * zj_inv, z2, -fx * xz * zj_inv, -fx * xz * yz, fx * __builtin_elementwise_fma(xz, xz, o2),
-                        -fx * yz, z2};
-      const f2 J1[7] = {z2, fy * zj_inv, -fy * yz * zj_inv, -fy * __builtin_elementwise_fma(yz, yz, o2), fy * xz * yz,
-                        fy * xz, z2};
-      const f2 J2[7] = {z2, z2, zj_inv, yz, -xz, z2, o2};
-      acc_local_f2<0b0111101>(fL, fv, J0, huber_ba2(swp * err[0]) * wp, err[0]);  // {0,2,3,4,5}
-      acc_local_f2<0b0111110>(fL, fv, J1, huber_ba2(swp * err[1]) * wp, err[1]);  // {1,2,3,4,5}
-      acc_local_f2<0b1011100>(fL, fv, J2, huber_ba2(swd * err[2]) * wd, err[2]);  // {2,3,4,6}
-    }
-  };
+    for (int d = 0; d < 3; d++) r.Xj[d] = f2{c.Xj_base[(size_t)pt.k0 * 3 + d], c.Xj_base[(size_t)pt.k1 * 3 + d]};
+  }
+}
+// a round from the stored records: every load unconditional (RoundPts), so that it can be issued a round ahead
+template <int MODE, bool RAYLDS>
+__device__ __forceinline__ void round_fetch(const LinChunk& c, int k00, PixWalk<RAYLDS>& pix, Round& r) {
+  const RoundPts pt(c, k00);
+  r.R0 = rec_load<MODE>(c.rec, pt.k0);
+  r.R1 = rec_load<MODE>(c.rec, pt.k1);
+  if constexpr (MODE == BA_MODE_RAYS) r.nI = f2{c.rec_n[pt.k0], c.rec_n[pt.k1]};
+  round_xj<MODE>(c, pt, r);
+  if constexpr (MODE == BA_MODE_CALIB_RAW) pix.next(pt.has1, r.Xj[0], r.Xj[1]);
+}
+// a live lane's round from the match data (fused pack): its records built, stored for later iterations, kept; in order
+template <int MODE>
+__device__ __forceinline__ void round_pack(const BaArgs& a, const BaParams& p, int e, int ix, int jx,
+                                           const LinChunk& c, const RoundPts& pt, Round& r) {
+  float n0 = 0.0f, n1 = 0.0f;
+  r.R0 = pack_record<MODE>(a, p, e, ix, jx, pt.k0, &n0);
+  n1 = n0;
+  if (pt.has1) r.R1 = pack_record<MODE>(a, p, e, ix, jx, pt.k1, &n1);
+  else r.R1 = r.R0;
+  rec_store<MODE>(c.rec, pt.k0, r.R0);
+  if (pt.has1) rec_store<MODE>(c.rec, pt.k1, r.R1);
+  if constexpr (MODE == BA_MODE_RAYS) {
+    c.rec_n[pt.k0] = n0;
+    if (pt.has1) c.rec_n[pt.k1] = n1;
+    r.nI = f2{n0, n1};
+  }
+  round_xj<MODE>(c, pt, r);
+}
+template <int MODE>  // the rows of round r of a live lane; kept apart from rows on purpose (BA)
+__device__ __forceinline__ void lin_round(const BaParams& p, const LinEdge& edge, Round& r, bool has1, RunSums& s) {
+  if constexpr (MODE == BA_MODE_CALIB_RAW) {
+    r.Xj[0] = r.Xj[2] * r.Xj[0];
+    r.Xj[1] = r.Xj[2] * r.Xj[1];
+  }
+  rows<MODE>(p, edge, rec_expand<MODE>(r.R0), rec_expand<MODE>(r.R1), r.nI, r.Xj, has1, s);
+}
+// the end of a round, for every thread of the block (lin_flush's contract): after BA_RUN_LEN rounds the run is flushed
+__device__ __forceinline__ void run_step(int& run, RunSums& s, LinLds& lds) {
+  if (++run == BA_RUN_LEN) {
+    run = 0;
+    lin_flush(s, lds);
+  }
+}
+
+// One block per (edge, chunk of its points), two points per lane and round. PACK: the first GN iteration of a call that
+// packs every edge builds each point's record itself (pack_record, the same values) and stores it for the later ones:
+// the pack's gathers (HBM-bound) run under this kernel's VALU-bound rows instead of as a separate launch before it.
+template <int MODE, bool PACK, bool RAYLDS = false>  // specialised per residual type: one mode's registers, not the union of three
+__global__ void __launch_bounds__(256, BA_LIN_WAVES) ba_lin_kernel(BaArgs a, BaParams p) {
+  if (*a.done) return;
+  // the plan's block table: edges grouped by target keyframe, consecutive blocks on one XCD (xcd_remap)
+  const int code = a.lin_tab[xcd_remap(blockIdx.x, gridDim.x)];
+  const int e = code / p.chunks, chunk = code - e * p.chunks;
+  const int ix = a.ii_rank[e], jx = a.jj_rank[e];
+  const LinEdge edge(a, ix, jx);
+  __shared__ LinLds lds;
+  if (threadIdx.x < BA_NSUM) lds.tot[threadIdx.x] = 0.0;
+  float4* const rec = rec_of_slot(a, a.rec_slot ? a.rec_slot[e] : e, p.N);
+  const float* const Xj = a.Xkf[jx];
+  const int per = (p.N + p.chunks - 1) / p.chunks, k_begin = chunk * per;
+  const LinChunk c = {rec,     reinterpret_cast<float*>(rec + p.N), Xj, (gfloat_p)(Xj + 2),
+                      k_begin, min(p.N, k_begin + per)};
+  PixWalk<RAYLDS> pix;
+  if constexpr (MODE == BA_MODE_CALIB_RAW) pix.init(a, p, c.k_begin);
+  RunSums sums = {};
   int run = 0;
-  // a block-uniform trip count: every lane reaches each run flush together (the pair flush swaps run sums between
-  // the lanes of a pair); a lane past the chunk's end skips the point work
-  if constexpr (PACK) {
-    for (int k00 = k_begin; k00 < k_end; k00 += 2 * blockDim.x) {
-      const int k0 = k00 + (int)threadIdx.x;
-      f2 xu = {0.0f, 0.0f}, yv = {0.0f, 0.0f};
-      if constexpr (MODE == BA_MODE_CALIB_RAW) pix_next(k0 + (int)blockDim.x < k_end, xu, yv);
-      if (k0 < k_end) {
-        const int k1 = k0 + (int)blockDim.x;
-        const bool has1 = k1 < k_end;
-        const int k1c = has1 ? k1 : k0;
-        float n0 = 0.0f, n1 = 0.0f;
-        float4 R0 = pack_record<MODE>(a, p, e, ix, jx, k0, &n0), R1;
-        n1 = n0;
-        if (has1) R1 = pack_record<MODE>(a, p, e, ix, jx, k1, &n1);
-        else R1 = R0;
-        rec_store<MODE>(rec, k0, R0);
-        if (has1) rec_store<MODE>(rec, k1, R1);
-        if constexpr (MODE == BA_MODE_RAYS) {
-          rec_n[k0] = n0;
-          if (has1) rec_n[k1] = n1;
-        }
-        f2 Xj[3];
-        if constexpr (MODE == BA_MODE_CALIB_RAW) {
-          Xj[2] = f2{Zj_base[(size_t)k0 * 3], Zj_base[(size_t)k1c * 3]};
-          Xj[0] = Xj[2] * xu;
-          Xj[1] = Xj[2] * yv;
-        } else {
-#pragma unroll
-          for (int c = 0; c < 3; c++) Xj[c] = f2{Xj_base[(size_t)k0 * 3 + c], Xj_base[(size_t)k1c * 3 + c]};
-        }
-        rows(rec_expand<MODE>(R0), rec_expand<MODE>(R1), f2{n0, n1}, Xj, has1);
+  if constexpr (PACK) {  // in order: a round's records are built, stored and used
+    for (int k00 = c.k_begin; k00 < c.k_end; k00 += 2 * blockDim.x) {
+      const RoundPts pt(c, k00);
+      Round cur;
+      if constexpr (MODE == BA_MODE_CALIB_RAW) pix.next(pt.has1, cur.Xj[0], cur.Xj[1]);
+      if (pt.live) {
+        round_pack<MODE>(a, p, e, ix, jx, c, pt, cur);
+        lin_round<MODE>(p, edge, cur, pt.has1, sums);
       }
-      if (++run == BA_RUN_LEN) {
-        run = 0;
-        flush();
-      }
+      run_step(run, sums, lds);
     }
   } else {
-    // software-pipelined: a lane loads the next round's records and X_j before it computes this round's rows, so
-    // the loads' HBM latency runs under the VALU work (the kernel holds 3 waves per SIMD, too few to hide it alone).
-    // Every load is unconditional (a lane past the chunk's end loads point k_begin and skips the rows): the hand-over
-    // nxt -> cur at the end of a round is then the only use of a load in flight, after the round's rows.
-    struct Round {
-      float4 R0, R1;  // as stored (rec_load)
-      f2 nI;          // rays: |Xi| of both points
-      f2 Xj[3];       // raw calib: {x_of_u[u], y_of_v[v], z_j}, multiplied out where the round is computed
-    };
-    auto fetch = [&](int k00, Round& r) {
-      const int k0 = k00 + (int)threadIdx.x < k_end ? k00 + (int)threadIdx.x : k_begin;
-      const int k1 = k0 + (int)blockDim.x < k_end ? k0 + (int)blockDim.x : k0;
-      r.R0 = rec_load<MODE>(rec, k0);
-      r.R1 = rec_load<MODE>(rec, k1);
-      if constexpr (MODE == BA_MODE_RAYS) r.nI = f2{rec_n[k0], rec_n[k1]};
-      if constexpr (MODE == BA_MODE_CALIB_RAW) {
-        r.Xj[2] = f2{Zj_base[(size_t)k0 * 3], Zj_base[(size_t)k1 * 3]};
-        pix_next(k00 + (int)threadIdx.x + (int)blockDim.x < k_end, r.Xj[0], r.Xj[1]);
-      } else {
-#pragma unroll
-        for (int c = 0; c < 3; c++) r.Xj[c] = f2{Xj_base[(size_t)k0 * 3 + c], Xj_base[(size_t)k1 * 3 + c]};
-      }
-    };
+    // software-pipelined: a lane loads the next round's records and X_j before it computes this round's rows, so the
+    // loads' HBM latency runs under the VALU work (3 waves per SIMD are too few to hide it alone). Every load is
+    // unconditional (round_fetch): the hand-over nxt -> cur is then a load's only use while in flight, after the rows.
     Round cur;
-    fetch(k_begin, cur);
-    for (int k00 = k_begin; k00 < k_end; k00 += 2 * blockDim.x) {
-      const int k0 = k00 + (int)threadIdx.x;
+    round_fetch<MODE>(c, c.k_begin, pix, cur);
+    for (int k00 = c.k_begin; k00 < c.k_end; k00 += 2 * blockDim.x) {
       Round nxt;
-      fetch(k00 + 2 * blockDim.x, nxt);
-      if (k0 < k_end) {
-        f2 nI = {0.0f, 0.0f};
-        if constexpr (MODE == BA_MODE_RAYS) nI = cur.nI;
-        if constexpr (MODE == BA_MODE_CALIB_RAW) {
-          cur.Xj[0] = cur.Xj[2] * cur.Xj[0];
-          cur.Xj[1] = cur.Xj[2] * cur.Xj[1];
-        }
-        rows(rec_expand<MODE>(cur.R0), rec_expand<MODE>(cur.R1), nI, cur.Xj, k0 + (int)blockDim.x < k_end);
-      }
-      if (++run == BA_RUN_LEN) {
-        run = 0;
-        flush();
-      }
+      round_fetch<MODE>(c, k00 + 2 * blockDim.x, pix, nxt);
+      const RoundPts pt(c, k00);
+      if (pt.live) lin_round<MODE>(p, edge, cur, pt.has1, sums);
+      run_step(run, sums, lds);
       cur = nxt;
     }
   }
-  flush();
-  if (threadIdx.x < 35) a.partials[(size_t)code * BA_NSUM + threadIdx.x] = s_tot[threadIdx.x];  // its own entry
+  lin_flush(sums, lds);
+  if (threadIdx.x < 35) a.partials[(size_t)code * BA_NSUM + threadIdx.x] = lds.tot[threadIdx.x];  // its own entry
 }
 
 // per-edge: sum chunk partials, M = A L A^T, g = A v with A the adjoint-inverse map of T_i.
@@ -680,12 +690,8 @@ __global__ void __launch_bounds__(64) ba_edge_kernel(BaArgs a, BaParams p, int E
         if (c0 + k < p.chunks) s += v[k];
     }
     if (t < 28) {
-      int r = 0, l = t;
-      while (l >= 7 - r) {
-        l -= 7 - r;
-        r++;
-      }
-      const int c = r + l;
+      int r, c;
+      tri_rc(t, &r, &c);
       s_L[r][c] = s;
       s_L[c][r] = s;
     } else {
@@ -711,12 +717,8 @@ __global__ void __launch_bounds__(64) ba_edge_kernel(BaArgs a, BaParams p, int E
   __syncthreads();
   double* out = a.edge_sums + (size_t)(e + p.edge_offset) * BA_NSUM;
   if (t < 28) {
-    int r = 0, l = t;
-    while (l >= 7 - r) {
-      l -= 7 - r;
-      r++;
-    }
-    const int c = r + l;
+    int r, c;
+    tri_rc(t, &r, &c);
     double s = 0.0;
     for (int k = 0; k < 7; k++) s += s_AL[r][k] * s_A[c][k];
     out[t] = s;
@@ -730,7 +732,18 @@ __global__ void __launch_bounds__(64) ba_edge_kernel(BaArgs a, BaParams p, int E
 
 }  // namespace m3s
 
-// ------------------------------------------------------------------------------------------
+// the one place the run-time mode becomes a template argument: f(std::integral_constant<int, MODE>{}) launches
+template <class F>
+static hipError_t ba_with_mode(int mode, F&& f) {
+  switch (mode) {
+    case BA_MODE_POINTS: return f(std::integral_constant<int, BA_MODE_POINTS>{});
+    case BA_MODE_RAYS: return f(std::integral_constant<int, BA_MODE_RAYS>{});
+    case BA_MODE_CALIB: return f(std::integral_constant<int, BA_MODE_CALIB>{});
+    case BA_MODE_CALIB_RAW: return f(std::integral_constant<int, BA_MODE_CALIB_RAW>{});
+  }
+  return hipErrorInvalidValue;
+}
+
 extern "C" hipError_t m3s_launch_ba_kf_compare(const BaKfCopy* kf, int Kp, int N, uint8_t* dirty, hipStream_t s) {
   if (Kp <= 0) return hipSuccess;
   const unsigned bx = (unsigned)std::min<size_t>(((size_t)4 * N + 255) / 256, 64);
@@ -744,39 +757,25 @@ extern "C" hipError_t m3s_launch_ba_pack(const BaArgs* a, const BaParams* p, int
   const size_t blocks = ((size_t)n_pack * tiles + 7) & ~(size_t)7;  // a multiple of 8: the XCD-contiguous tile order
   if (blocks > 0x7fffffff) return hipErrorInvalidValue;
   const dim3 g((unsigned)blocks);
-  if (p->mode == BA_MODE_CALIB)
-    hipLaunchKernelGGL(m3s::ba_pack_kernel<BA_MODE_CALIB>, g, dim3(256), 0, s, *a, *p, n_pack, tiles);
-  else if (p->mode == BA_MODE_CALIB_RAW)
-    hipLaunchKernelGGL(m3s::ba_pack_kernel<BA_MODE_CALIB_RAW>, g, dim3(256), 0, s, *a, *p, n_pack, tiles);
-  else if (p->mode == BA_MODE_RAYS)
-    hipLaunchKernelGGL(m3s::ba_pack_kernel<BA_MODE_RAYS>, g, dim3(256), 0, s, *a, *p, n_pack, tiles);
-  else
-    hipLaunchKernelGGL(m3s::ba_pack_kernel<BA_MODE_POINTS>, g, dim3(256), 0, s, *a, *p, n_pack, tiles);
-  return hipGetLastError();
+  return ba_with_mode(p->mode, [&](auto mode) {
+    hipLaunchKernelGGL(m3s::ba_pack_kernel<decltype(mode)::value>, g, dim3(256), 0, s, *a, *p, n_pack, tiles);
+    return hipGetLastError();
+  });
 }
 
 // pack (first iteration of a call whose pack was deferred): the linearisation also builds and stores the records
 extern "C" hipError_t m3s_launch_ba_lin(const BaArgs* a, const BaParams* p, int E_local, int pack, hipStream_t s) {
   if (E_local <= 0) return hipSuccess;
   const dim3 g(E_local * p->chunks);
-#define BA_LIN_LAUNCH(M, L)                                                                     \
-  do {                                                                                          \
-    if (pack)                                                                                   \
-      hipLaunchKernelGGL((m3s::ba_lin_kernel<M, true, L>), g, dim3(256), 0, s, *a, *p);           \
-    else                                                                                        \
-      hipLaunchKernelGGL((m3s::ba_lin_kernel<M, false, L>), g, dim3(256), 0, s, *a, *p);          \
-  } while (0)
-  if (p->mode == BA_MODE_POINTS)
-    BA_LIN_LAUNCH(BA_MODE_POINTS, false);
-  else if (p->mode == BA_MODE_RAYS)
-    BA_LIN_LAUNCH(BA_MODE_RAYS, false);
-  else if (p->mode == BA_MODE_CALIB_RAW && p->W + p->H <= BA_RAY_LDS)
-    BA_LIN_LAUNCH(BA_MODE_CALIB_RAW, true);
-  else if (p->mode == BA_MODE_CALIB_RAW)
-    BA_LIN_LAUNCH(BA_MODE_CALIB_RAW, false);
-  else
-    BA_LIN_LAUNCH(BA_MODE_CALIB, false);
-#undef BA_LIN_LAUNCH
-  hipLaunchKernelGGL(m3s::ba_edge_kernel, dim3(E_local), dim3(64), 0, s, *a, *p, E_local);
-  return hipGetLastError();
+  return ba_with_mode(p->mode, [&](auto mode) {
+    constexpr int M = decltype(mode)::value;
+    constexpr bool RAW = M == BA_MODE_CALIB_RAW;         // raw calib has a second instance, for ray tables that fit LDS
+    const bool lds = RAW && p->W + p->H <= BA_RAY_LDS;  // (for the other modes both names below are the one instance)
+    void (*lin)(BaArgs, BaParams) =
+        pack ? (lds ? m3s::ba_lin_kernel<M, true, RAW> : m3s::ba_lin_kernel<M, true, false>)
+             : (lds ? m3s::ba_lin_kernel<M, false, RAW> : m3s::ba_lin_kernel<M, false, false>);
+    hipLaunchKernelGGL(lin, g, dim3(256), 0, s, *a, *p);
+    hipLaunchKernelGGL(m3s::ba_edge_kernel, dim3(E_local), dim3(64), 0, s, *a, *p, E_local);
+    return hipGetLastError();
+  });
 }

@@ -45,6 +45,17 @@ __device__ __forceinline__ bool ba_asm_element(int b, int nL, int t, int* li) {
   return t < 7;
 }
 
+// the inverse of ba_asm_element's map: (row, column), r <= c, of element t < 28 of the upper-stored 7x7 normal block
+__device__ __forceinline__ void tri_rc(int t, int* r, int* c) {
+  int row = 0;
+  while (t >= 7 - row) {
+    t -= 7 - row;
+    row++;
+  }
+  *r = row;
+  *c = row + t;
+}
+
 // that element: the contributions of the plan's CSR row of item b, added strictly in CSR order (deterministic:
 // identical on every rank and in both solves); the indices and values of 4 entries in flight at a time
 __device__ __forceinline__ double ba_asm_sum(const BaArgs& a, int b, int nL, int li) {

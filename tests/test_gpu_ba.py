@@ -291,8 +291,8 @@ def test_ba_medium_graph_vs_fp64_truth(mode):
 @pytest.mark.parametrize("mode", ["rays", "calib"])
 def test_ba_full_chunk_runs_vs_fp64_truth(mode, monkeypatch):
     """6 keyframes at 128x192 = 24576 points per edge, one full linearisation chunk: every lane walks 48 point
-    rounds, so the fp32 runs are flushed into the fp64 accumulators several times (the smaller graphs end
-    inside the first run). Poses within 1e-5 of the oracle's fp64 truth."""
+    rounds, the longest fp32 runs a chunk can hold (BA_RUN_LEN is 64 rounds), flushed into the fp64 sums once, at the
+    chunk's end (the smaller graphs end after a few rounds). Poses within 1e-5 of the oracle's fp64 truth."""
     from m3s.synthetic import make_graph, two_way
 
     # the production chunk length of large graphs (small graphs get shorter chunks, abi_ba.cpp ba_chunks)
