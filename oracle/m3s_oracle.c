@@ -625,7 +625,7 @@ static void m3o_row(const float* Ji_local, const float* ti, const float* qi, con
 static void m3o_linearize_edge(const m3o_ba_params* P, const float* Twc, const float* Xs,
                                const float* Cs, int N, int ix, int jx, const int64_t* idx,
                                const uint8_t* valid_match, const float* Q, double* Hout /*4x7x7*/,
-                               double* gout /*2x7*/) {
+                               double* gout /*2x7*/, double* chi2out /*1, or NULL*/) {
   const float *ti = &Twc[ix * 8], *qi = &Twc[ix * 8 + 3], *si = &Twc[ix * 8 + 7];
   const float *tj = &Twc[jx * 8], *qj = &Twc[jx * 8 + 3], *sj = &Twc[jx * 8 + 7];
   float tij[3], qij[4], sij[1];
@@ -635,10 +635,12 @@ static void m3o_linearize_edge(const m3o_ba_params* P, const float* Twc, const f
   memset(hij, 0, sizeof(hij));
   memset(vi, 0, sizeof(vi));
   memset(vj, 0, sizeof(vj));
+  double chi2 = 0.0; /* sum of w e^2 over every row: per-row product in `float`, summed in fp64 in both orders */
   /* reference order: per thread slot t (0..255) 105 + 7 + 7 floats */
   float* rf = g_ref_order ? (float*)calloc((size_t)256 * 119, sizeof(float)) : NULL;
 #define M3O_ACC(Jx_, w_, e_)                                                                      \
   do {                                                                                            \
+    chi2 += (double)((w_) * (e_) * (e_));                                                         \
     if (rf) {                                                                                     \
       float* sl = rf + (size_t)(k % 256) * 119;                                                   \
       m3o_accum_row_f(sl, sl + 105, sl + 112, Jx_, w_, e_);                                       \
@@ -747,6 +749,7 @@ static void m3o_linearize_edge(const m3o_ba_params* P, const float* Twc, const f
     (void)Jl;
   }
 #undef M3O_ACC
+  if (chi2out) *chi2out = chi2;
   if (rf) {  /* the float block reductions, in the reference's order (gs first, then hij) */
     for (int n = 0; n < 7; n++) {
       vi[n] = (double)m3o_block_reduce(rf + 105 + n, 119);
@@ -779,10 +782,12 @@ static void m3o_linearize_edge(const m3o_ba_params* P, const float* Twc, const f
 
 /* Linearise every edge; Hs (4,E,7,7) and gs (2,E,7) fp64, reference layout (:757-758).
  * ii/jj here are already dense ranks into Twc/Xs (the kernel's ii_edge/jj_edge). */
-void m3o_ba_linearize(int mode, const float* Twc, const float* Xs, const float* Cs, int N, int E,
-                      const int64_t* ii_rank, const int64_t* jj_rank, const int64_t* idx,
-                      const uint8_t* valid_match, const float* Q, const float* params /*12*/,
-                      double* Hs, double* gs) {
+/* m3o_ba_linearize plus, when chi2 is not NULL, chi2[e] = sum over every row of w e^2 (the weighted squared
+ * residual the edge's g and H belong to; by Cauchy-Schwarz g_a^2 <= H_aa chi2). */
+void m3o_ba_linearize_chi2(int mode, const float* Twc, const float* Xs, const float* Cs, int N, int E,
+                           const int64_t* ii_rank, const int64_t* jj_rank, const int64_t* idx,
+                           const uint8_t* valid_match, const float* Q, const float* params /*12*/,
+                           double* Hs, double* gs, double* chi2) {
   m3o_ba_params P;
   P.mode = mode;
   P.sigma_a = params[0];
@@ -801,11 +806,18 @@ void m3o_ba_linearize(int mode, const float* Twc, const float* Xs, const float* 
   for (int e = 0; e < E; e++) {
     double H4[196], g2[14];
     m3o_linearize_edge(&P, Twc, Xs, Cs, N, (int)ii_rank[e], (int)jj_rank[e], idx + (size_t)e * N,
-                       valid_match + (size_t)e * N, Q + (size_t)e * N, H4, g2);
+                       valid_match + (size_t)e * N, Q + (size_t)e * N, H4, g2, chi2 ? &chi2[e] : NULL);
     for (int b = 0; b < 4; b++)
       memcpy(&Hs[((size_t)b * E + e) * 49], &H4[b * 49], 49 * sizeof(double));
     for (int b = 0; b < 2; b++) memcpy(&gs[((size_t)b * E + e) * 7], &g2[b * 7], 7 * sizeof(double));
   }
+}
+
+void m3o_ba_linearize(int mode, const float* Twc, const float* Xs, const float* Cs, int N, int E,
+                      const int64_t* ii_rank, const int64_t* jj_rank, const int64_t* idx,
+                      const uint8_t* valid_match, const float* Q, const float* params /*12*/,
+                      double* Hs, double* gs) {
+  m3o_ba_linearize_chi2(mode, Twc, Xs, Cs, N, E, ii_rank, jj_rank, idx, valid_match, Q, params, Hs, gs, NULL);
 }
 
 /* Dense fp64 Cholesky solve of A x = b in place (A n x n row-major, lower factor).

@@ -46,6 +46,9 @@ def lib64():
             + [ctypes.c_int, ctypes.c_double, _f64p]
         )
         L.m3o_gauss_newton.restype = ctypes.c_int
+        # the F64 build turns every float* of the entry point into double*
+        L.m3o_ba_linearize_chi2.argtypes = [ctypes.c_int, _f64p, _f64p, _f64p, ctypes.c_int, ctypes.c_int,
+                                            _i64p, _i64p, _i64p, _u8p, _f64p, _f64p, _f64p, _f64p, _f64p]
         _LIB64 = L
     return _LIB64
 
@@ -73,6 +76,7 @@ def lib():
         L.m3o_gauss_newton.restype = ctypes.c_int
         L.m3o_ba_linearize.argtypes = [ctypes.c_int, _f32p, _f32p, _f32p, ctypes.c_int, ctypes.c_int,
                                        _i64p, _i64p, _i64p, _u8p, _f32p, _f32p, _f64p, _f64p]
+        L.m3o_ba_linearize_chi2.argtypes = L.m3o_ba_linearize.argtypes + [_f64p]
         L.m3o_pose_retr.argtypes = [_f32p, _f32p, ctypes.c_int, ctypes.c_int]
         L.m3o_exp_sim3.argtypes = [_f32p, _f32p]
         L.m3o_norm3.argtypes = [_f32p, _f32p, ctypes.c_int64]
@@ -229,6 +233,47 @@ def ba_linearize(mode, Twc, Xs, Cs, ii_rank, jj_rank, idx, valid, Q, params):
                            _p(_c(valid, np.uint8), _u8p), _p(_c(Q, np.float32), _f32p),
                            _p(_c(params, np.float32), _f32p), _p(Hs, _f64p), _p(gs, _f64p))
     return Hs, gs
+
+
+def _ba_linearize_chi2(L, ft, fp, mode, Twc, Xs, Cs, ii_rank, jj_rank, idx, valid, Q, params):
+    Twc, Xs, Cs = _c(Twc, ft), _c(Xs, ft), _c(Cs, ft)
+    N = Xs.shape[1]
+    ii_rank, jj_rank = _c(ii_rank, np.int64), _c(jj_rank, np.int64)
+    E = ii_rank.shape[0]
+    Hs = np.zeros((4, E, 7, 7), np.float64)
+    gs = np.zeros((2, E, 7), np.float64)
+    chi2 = np.zeros(E, np.float64)
+    L.m3o_ba_linearize_chi2(_MODES[mode], _p(Twc, fp), _p(Xs, fp), _p(Cs, fp), N, E, _p(ii_rank, _i64p),
+                            _p(jj_rank, _i64p), _p(_c(idx, np.int64), _i64p), _p(_c(valid, np.uint8), _u8p),
+                            _p(_c(Q, ft), fp), _p(_c(params, ft), fp), _p(Hs, _f64p), _p(gs, _f64p), _p(chi2, _f64p))
+    return Hs, gs, chi2
+
+
+def ba_linearize_chi2(mode, Twc, Xs, Cs, ii_rank, jj_rank, idx, valid, Q, params):
+    """``ba_linearize`` plus chi2 (E,): per edge the sum over every row of w e^2 (each product in fp32, summed in
+    fp64, in both orders of ``set_ref_order``). Hs and gs are those of ``ba_linearize``."""
+    return _ba_linearize_chi2(lib(), np.float32, _f32p, mode, Twc, Xs, Cs, ii_rank, jj_rank, idx, valid, Q, params)
+
+
+def ba_linearize_f64(mode, Twc, Xs, Cs, ii_rank, jj_rank, idx, valid, Q, params):
+    """fp64 truth of ``ba_linearize`` (every float of the restatement computed in double): Hs (4,E,7,7), gs (2,E,7)."""
+    return ba_linearize_chi2_f64(mode, Twc, Xs, Cs, ii_rank, jj_rank, idx, valid, Q, params)[:2]
+
+
+def ba_linearize_chi2_f64(mode, Twc, Xs, Cs, ii_rank, jj_rank, idx, valid, Q, params):
+    """fp64 truth of ``ba_linearize_chi2``: (Hs, gs, chi2)."""
+    return _ba_linearize_chi2(lib64(), np.float64, _f64p, mode, Twc, Xs, Cs, ii_rank, jj_rank, idx, valid, Q, params)
+
+
+def edge_row_from_blocks(Hs, gs):
+    """The device's (E, 36) edge-sum row from the reference layout: M = Hs[3] as its upper triangle in row-major
+    order (``np.triu_indices(7)``) in columns 0..27, g = gs[1] in columns 28..34, column 35 (padding) zero."""
+    E = Hs.shape[1]
+    iu = np.triu_indices(7)
+    row = np.zeros((E, 36), np.float64)
+    row[:, :28] = Hs[3][:, iu[0], iu[1]]
+    row[:, 28:35] = gs[1]
+    return row
 
 
 def pose_retr(Twc, dx, num_fix=1):

@@ -290,9 +290,13 @@ def test_ba_medium_graph_vs_fp64_truth(mode):
 
 @pytest.mark.parametrize("mode", ["rays", "calib"])
 def test_ba_full_chunk_runs_vs_fp64_truth(mode, monkeypatch):
-    """6 keyframes at 128x192 = 24576 points per edge, one full linearisation chunk: every lane walks 48 point
-    rounds, the longest fp32 runs a chunk can hold (BA_RUN_LEN is 64 rounds), flushed into the fp64 sums once, at the
-    chunk's end (the smaller graphs end after a few rounds). Poses within 1e-5 of the oracle's fp64 truth."""
+    """6 keyframes at 128x192 = 24576 points per edge, one full linearisation chunk: every lane loads 48 point
+    rounds, the most a production chunk holds (BA_RUN_LEN is 64 rounds), flushed into the fp64 sums once, at the
+    chunk's end (the smaller graphs end after a few rounds). Poses within 1e-5 of the oracle's fp64 truth.
+
+    make_graph's six cameras stand 60 degrees apart: 2.0 % of this graph's points carry weight (a valid match with
+    Q > 1.5), on 10 of its 22 edges, so the 48-round fp32 runs add mostly exact zeros. The densely weighted version,
+    with the edge sums themselves compared with fp64 and a chunk of 65 rounds: tests/test_gpu_ba_edges.py."""
     from m3s.synthetic import make_graph, two_way
 
     # the production chunk length of large graphs (small graphs get shorter chunks, abi_ba.cpp ba_chunks)
@@ -465,7 +469,11 @@ def test_pack_tiles_with_ragged_last_tile(mode, monkeypatch):
     """The pack kernel's tiles (ba.hip ba_pack_kernel: one block per 4096 points of one edge, 4 points per lane per
     trip, loads at a clamped index) on 72x100 = 7200 points per edge: one full tile and a ragged one whose last
     trip is partly past the edge. Its records must equal the fused pack's (ba_lin_kernel<PACK>: pack_record, one
-    point at a time, every load in order) bit for bit, and the poses sit within 1e-5 of the fp64 truth."""
+    point at a time, every load in order) bit for bit, and the poses sit within 1e-5 of the fp64 truth.
+
+    6.8 % of this graph's points carry weight (a valid match with Q > 1.5), on 14 of its 38 edges; the ragged tile's
+    32 tail points carry weight on 5 edges. The densely weighted version, with the edge sums themselves compared with
+    fp64 (two pack tiles, a last tile of 4 points, a ragged trip): tests/test_gpu_ba_edges.py, cases n4100, n5123."""
     from m3s.synthetic import make_graph, two_way
 
     H, W = 72, 100

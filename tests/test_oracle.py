@@ -264,3 +264,41 @@ def test_track_restatement_matches_reference_at_config_size(golden, case):
     assert it == int(g[f"{case}_iters"])
     np.testing.assert_allclose(Tf, g[f"{case}_T_WCf"][0], atol=1e-5)
     np.testing.assert_allclose(kX[g[f"{case}_sub"]], g[f"{case}_kf_X_sub"], atol=1e-5, rtol=1e-5)
+
+
+def test_ba_chi2_bounds_the_gradient(golden):
+    """m3o_ba_linearize_chi2 (both builds, both orders of the fp32 one): per edge chi2 = sum w e^2 bounds the gradient,
+    chi2 >= g_a^2 / M_aa for every a (Cauchy-Schwarz: g_a = sum w e J_a, M_aa = sum w J_a^2), and is exactly 0 on an
+    edge with no weighted point. Hs and gs are those of m3o_ba_linearize, bit for bit. The sums the inequality holds
+    for exactly are of real products; each stored product carries one rounding of its format, hence the slack of a
+    few roundings (1e-6 fp32, 1e-14 fp64) on edges whose rows are far from parallel."""
+    g = golden("ba_6kf_24x32.npz")
+    H, W = 24, 32
+    ii, jj = np.concatenate((g["ii"], g["jj"])), np.concatenate((g["jj"], g["ii"]))
+    valid = g["valid2"][..., 0].copy()
+    valid[3] = False    # an edge with no weighted point
+    sig = {"points": (0.05, 0.0), "rays": (0.003, 10.0), "calib": (1.0, 10.0)}
+    for mode in ("points", "rays", "calib"):
+        Xs = O.backproject_constrain(g["Xs"], g["K"], (H, W)) if mode == "calib" else g["Xs"]
+        p = O.ba_params(mode, *sig[mode], 0.0, 1.5, K=g["K"], height=H, width=W, pixel_border=-10, z_eps=1e-6)
+        args = (mode, g["Twc0"], Xs, g["Cs"][..., 0], ii, jj, g["idx2"], valid, g["Q2"][..., 0], p)
+        outs = [(O.ba_linearize_chi2_f64(*args), 1e-14)]
+        for order in (0, 1):
+            O.set_ref_order(order)
+            try:
+                Hs, gs = O.ba_linearize(*args)
+                out = O.ba_linearize_chi2(*args)
+            finally:
+                O.set_ref_order(0)
+            assert np.array_equal(out[0], Hs) and np.array_equal(out[1], gs)
+            outs.append((out, 1e-6))
+        weighted = 0
+        for (Hs, gs, chi2), slack in outs:
+            assert chi2.shape == (ii.shape[0],) and chi2[3] == 0.0 and not Hs[:, 3].any() and not gs[:, 3].any()
+            M, gv = Hs[3], gs[1]
+            for e in np.flatnonzero(chi2 > 0):
+                d = np.diagonal(M[e])
+                assert (d > 0).all()
+                assert (chi2[e] * (1 + slack) >= gv[e] ** 2 / d).all(), (mode, e)
+            weighted = int((chi2 > 0).sum())
+        assert weighted >= 10
