@@ -295,6 +295,99 @@ __device__ __forceinline__ double wave_sum(double v) {
   return v;
 }
 
+// ---- cross-lane step primitives without LDS (the ds_bpermute of __shfl_xor): the half-exchange steps of a wave64
+// reduction. Lanes l and l^32 (v_permlane32_swap: the two halves of a register pair trade places, no selects), l and
+// l^16 (v_permlane16_swap), then within each 16-lane row l^8 (DPP row_ror:8), the 8-lane mirror pairs
+// (row_half_mirror), l^2 and l^1 (quad_perm). Every control reads a written lane for every lane, so no bound_ctrl ----
+enum : int {
+  DPP_ROW_ROR8 = 0x128,     // lane l reads l^8 of its row
+  DPP_HALF_MIRROR = 0x141,  // lane l reads 7 - l of its 8-lane half row
+  DPP_QUAD_2301 = 0x4E,     // lane l reads l^2
+  DPP_QUAD_1032 = 0xB1      // lane l reads l^1
+};
+// the four in-row steps in the order the reductions take them
+__device__ constexpr int dpp_row_ctrl(int sel) {
+  return sel == 0 ? DPP_ROW_ROR8 : sel == 1 ? DPP_HALF_MIRROR : sel == 2 ? DPP_QUAD_2301 : DPP_QUAD_1032;
+}
+
+template <int CTRL>
+__device__ __forceinline__ int dpp_b32(int x) {
+  return __builtin_amdgcn_mov_dpp(x, CTRL, 0xF, 0xF, false);
+}
+
+// a and b trade their upper-32 / lower-32 lane halves (W = 32) or, within each 32-lane half, their upper-16 /
+// lower-16 quarters (W = 16): afterwards the lower part of a holds a, its upper part b's lower part; the lower part
+// of b holds a's upper part, its upper part b. So op(a, b) leaves op(a, a(partner)) in the lower part and
+// op(b, b(partner)) in the upper part: one step of a reduce-scatter for two values at once
+template <int W>
+__device__ __forceinline__ void lane_swap(int& a, int& b) {
+  static_assert(W == 32 || W == 16, "half or quarter exchange");
+  if constexpr (W == 32) {
+    const auto r = __builtin_amdgcn_permlane32_swap(a, b, false, false);
+    a = (int)r[0];
+    b = (int)r[1];
+  } else {
+    const auto r = __builtin_amdgcn_permlane16_swap(a, b, false, false);
+    a = (int)r[0];
+    b = (int)r[1];
+  }
+}
+
+__device__ __forceinline__ double dpp_f64(double v, int ctrl_sel) {
+  int2 x = __builtin_bit_cast(int2, v);
+  switch (ctrl_sel) {  // compile-time after unrolling
+    case 0: x.x = dpp_b32<dpp_row_ctrl(0)>(x.x); x.y = dpp_b32<dpp_row_ctrl(0)>(x.y); break;
+    case 1: x.x = dpp_b32<dpp_row_ctrl(1)>(x.x); x.y = dpp_b32<dpp_row_ctrl(1)>(x.y); break;
+    case 2: x.x = dpp_b32<dpp_row_ctrl(2)>(x.x); x.y = dpp_b32<dpp_row_ctrl(2)>(x.y); break;
+    default: x.x = dpp_b32<dpp_row_ctrl(3)>(x.x); x.y = dpp_b32<dpp_row_ctrl(3)>(x.y); break;
+  }
+  return __builtin_bit_cast(double, x);
+}
+
+// lane_swap of two doubles; returns a' + b': lanes of the lower part hold a + a(partner), the upper part b + b(partner)
+template <int W>
+__device__ __forceinline__ double swap_add(double a, double b) {
+  int2 xa = __builtin_bit_cast(int2, a), xb = __builtin_bit_cast(int2, b);
+  lane_swap<W>(xa.x, xb.x);
+  lane_swap<W>(xa.y, xb.y);
+  return __builtin_bit_cast(double, xa) + __builtin_bit_cast(double, xb);
+}
+
+// one DPP step of a reduce-scatter: n live sums -> ceil(n/2); the lanes with `bit` set keep the upper half
+template <int N, int SEL>
+__device__ __forceinline__ void dpp_step(double* v, bool upper) {
+  constexpr int H = (N + 1) / 2;
+#pragma unroll
+  for (int i = 0; i < H; i++) {
+    const double lo = v[i], hi = i + H < N ? v[i + H] : 0.0;
+    const double keep = upper ? hi : lo, give = upper ? lo : hi;
+    v[i] = keep + dpp_f64(give, SEL);
+  }
+}
+
+// The integer forms (refine.hip's level-start exchanges). Two values a and b, reduced over the wave by OP
+// (associative and commutative: the order of the steps does not show in the result): the half exchange scatters
+// them, a to the lower 32 lanes and b to the upper 32, the quarter exchange and the four row steps finish each in
+// its half. Lane 0 returns the wave's a, lane 32 its b (every lane of a half holds its half's value).
+template <typename OP>
+__device__ __forceinline__ int wave_reduce2(int a, int b, OP op) {
+  lane_swap<32>(a, b);
+  int x = op(a, b), y = x;
+  lane_swap<16>(x, y);
+  x = op(x, y);
+  x = op(x, dpp_b32<DPP_ROW_ROR8>(x));
+  x = op(x, dpp_b32<DPP_HALF_MIRROR>(x));
+  x = op(x, dpp_b32<DPP_QUAD_2301>(x));
+  x = op(x, dpp_b32<DPP_QUAD_1032>(x));
+  return x;
+}
+
+// two signed 16-bit fields per dword: the elementwise minimum (v_pk_min_i16)
+typedef short i16x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ int pk_min_i16(int a, int b) {
+  return __builtin_bit_cast(int, __builtin_elementwise_min(__builtin_bit_cast(i16x2, a), __builtin_bit_cast(i16x2, b)));
+}
+
 // Bijective block remap (cdna guide §5 "XCD swizzle"): hardware deals block b to XCD b % 8; this
 // returns the logical block so that each XCD gets one contiguous run of logical blocks.
 __device__ __forceinline__ int xcd_remap(int b, int nb) {

@@ -421,34 +421,29 @@ __device__ __forceinline__ LevelWin level_window(const TileCtx& t, bool active, 
   const int lane = t.lane, wid = t.wid;
   // bbox of the inlier centres (within 16 px of pixel + the tile's flow estimate t.fu/t.fv)
   const bool inl = active && abs(cu - t.u_pix - t.fu) <= 16 && abs(cv - t.v_pix - t.fv) <= 16;
-  int mnu = inl ? cu : INT_MAX, mxu = inl ? cu : INT_MIN;
-  int mnv = inl ? cv : INT_MAX, mxv = inl ? cv : INT_MIN;
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    mnu = min(mnu, __shfl_xor(mnu, off, 64));
-    mxu = max(mxu, __shfl_xor(mxu, off, 64));
-    mnv = min(mnv, __shfl_xor(mnv, off, 64));
-    mxv = max(mxv, __shfl_xor(mxv, off, 64));
-  }
+  // Both bounds as minima of signed 16-bit pairs, one packed instruction per step for two of them: lo = {mnu, mnv},
+  // hi = {~mxu, ~mxv} (~x = -x - 1 reverses the order, and is one instruction for both fields). H, W < 32768
+  // (m3s_refine_tile_ok), so a centre inside the image fits with room for the sentinel: a lane that is no inlier holds
+  // 0x7fff in every field, neutral for the minimum, which reads back as mn = 32767 > mx = -32768 when no lane of the
+  // block is one. The pack saturates (v_cvt_pk_i16_i32): a centre outside that range (a caller's p1 past the image)
+  // gives a window that is not its cover, and the lane is then a window outlier like any other (refine_level's g.in
+  // is tested in 32 bits against the window that was placed). Reduced by wave_reduce2 (DPP and permlane swaps, no
+  // LDS round trip): lane 0 holds the wave's lo, lane 32 its hi.
+  constexpr int NONE = 0x7fff7fff;
+  const int pk = __builtin_bit_cast(int, __builtin_amdgcn_cvt_pk_i16(cu, cv));
+  const int red = wave_reduce2(inl ? pk : NONE, inl ? ~pk : NONE, [](int a, int b) { return pk_min_i16(a, b); });
   __syncthreads();  // previous level's readers of s_red / lds are done
-  if (lane == 0) {
-    s_red[wid][0] = mnu;
-    s_red[wid][1] = mxu;
-    s_red[wid][2] = mnv;
-    s_red[wid][3] = mxv;
-  }
+  if ((lane & 31) == 0) s_red[wid][lane >> 5] = red;
   __syncthreads();
-  mnu = s_red[0][0];
-  mxu = s_red[0][1];
-  mnv = s_red[0][2];
-  mxv = s_red[0][3];
+  int lo = s_red[0][0], hi = s_red[0][1];
 #pragma unroll
   for (int w = 1; w < RT_WAVES; w++) {
-    mnu = min(mnu, s_red[w][0]);
-    mxu = max(mxu, s_red[w][1]);
-    mnv = min(mnv, s_red[w][2]);
-    mxv = max(mxv, s_red[w][3]);
+    lo = pk_min_i16(lo, s_red[w][0]);
+    hi = pk_min_i16(hi, s_red[w][1]);
   }
+  // unpacked here: the placement below is 32-bit arithmetic (mxu + 3d passes 32767 at W = 32767)
+  hi = ~hi;
+  int mnu = (int)(short)lo, mnv = lo >> 16, mxu = (int)(short)hi, mxv = hi >> 16;
   if (mnu > mxu) {  // no inlier: any window (every active lane is an outlier)
     mnu = mxu = 0;
     mnv = mxv = 0;
@@ -791,16 +786,12 @@ template <bool XCHG_CMAX>
 __device__ __forceinline__ float tile_flow(TileCtx& t, bool active, int cu, int cv, int tx, int ty, float cmax_w,
                                            int (*s_red)[4]) {
   float cmax_b = 0.0f;
-  int su = active ? cu - t.u_pix : 0, sv = active ? cv - t.v_pix : 0, na = active ? 1 : 0;
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    su += __shfl_xor(su, off, 64);
-    sv += __shfl_xor(sv, off, 64);
-    na += __shfl_xor(na, off, 64);
-  }
+  // the two displacement sums by wave_reduce2 (32-bit adds; lane 0 holds the wave's su, lane 32 its sv), the count
+  // of active lanes from the ballot
+  const int sum = wave_reduce2(active ? cu - t.u_pix : 0, active ? cv - t.v_pix : 0, [](int a, int b) { return a + b; });
+  const int na = __popcll(__ballot(active));
+  if ((t.lane & 31) == 0) s_red[t.wid][t.lane >> 5] = sum;
   if (t.lane == 0) {
-    s_red[t.wid][0] = su;
-    s_red[t.wid][1] = sv;
     s_red[t.wid][2] = na;
     if constexpr (XCHG_CMAX) s_red[t.wid][3] = __float_as_int(cmax_w);
   }

@@ -368,53 +368,10 @@ typedef __attribute__((address_space(1))) unsigned long long gull;
 #define GN_PPT (1024 / GN_THREADS)  // points per thread per round (1024 per block): record loads issued before any math
 
 // ---- the 36 fp64 sums of a wave, reduce-scattered over its lanes (deterministic, no LDS) ----
-// Six half-exchange steps: lanes l and l^32 (v_permlane32_swap: the two halves of a register pair trade places,
-// no selects), l and l^16 (v_permlane16_swap), then within each 16-lane row l^8 (DPP row_ror:8), the 8-lane
-// mirror pairs (row_half_mirror), l^2 and l^1 (quad_perm). At every step a lane keeps one half of its current
-// sums and adds the partner's copy of that half. Afterwards lane gn_lane_of(c) holds the wave's total of sum c
-// (the other 28 lanes hold padding zeros). Fixed order: identical in every block and every run.
-__device__ __forceinline__ double dpp_f64(double v, int ctrl_sel) {
-  int2 x = __builtin_bit_cast(int2, v);
-  switch (ctrl_sel) {  // compile-time after unrolling
-    case 0: x.x = __builtin_amdgcn_mov_dpp(x.x, 0x128, 0xF, 0xF, false); x.y = __builtin_amdgcn_mov_dpp(x.y, 0x128, 0xF, 0xF, false); break;
-    case 1: x.x = __builtin_amdgcn_mov_dpp(x.x, 0x141, 0xF, 0xF, false); x.y = __builtin_amdgcn_mov_dpp(x.y, 0x141, 0xF, 0xF, false); break;
-    case 2: x.x = __builtin_amdgcn_mov_dpp(x.x, 0x4E, 0xF, 0xF, false); x.y = __builtin_amdgcn_mov_dpp(x.y, 0x4E, 0xF, 0xF, false); break;
-    default: x.x = __builtin_amdgcn_mov_dpp(x.x, 0xB1, 0xF, 0xF, false); x.y = __builtin_amdgcn_mov_dpp(x.y, 0xB1, 0xF, 0xF, false); break;
-  }
-  return __builtin_bit_cast(double, x);
-}
-
-// a and b trade their upper-32 / lower-32 lane halves (W = 32) or, within each 32-lane half, their upper-16 /
-// lower-16 quarters (W = 16); returns a' + b': lanes of the lower part hold a + a(partner), the upper part b + b(partner)
-template <int W>
-__device__ __forceinline__ double swap_add(double a, double b) {
-  const int2 xa = __builtin_bit_cast(int2, a), xb = __builtin_bit_cast(int2, b);
-  int2 na, nb;
-  if constexpr (W == 32) {
-    const auto lo = __builtin_amdgcn_permlane32_swap(xa.x, xb.x, false, false);
-    const auto hi = __builtin_amdgcn_permlane32_swap(xa.y, xb.y, false, false);
-    na = int2{(int)lo[0], (int)hi[0]};
-    nb = int2{(int)lo[1], (int)hi[1]};
-  } else {
-    const auto lo = __builtin_amdgcn_permlane16_swap(xa.x, xb.x, false, false);
-    const auto hi = __builtin_amdgcn_permlane16_swap(xa.y, xb.y, false, false);
-    na = int2{(int)lo[0], (int)hi[0]};
-    nb = int2{(int)lo[1], (int)hi[1]};
-  }
-  return __builtin_bit_cast(double, na) + __builtin_bit_cast(double, nb);
-}
-
-// one DPP step: n live sums -> ceil(n/2); the lanes with `bit` set keep the upper half
-template <int N, int SEL>
-__device__ __forceinline__ void dpp_step(double* v, bool upper) {
-  constexpr int H = (N + 1) / 2;
-#pragma unroll
-  for (int i = 0; i < H; i++) {
-    const double lo = v[i], hi = i + H < N ? v[i + H] : 0.0;
-    const double keep = upper ? hi : lo, give = upper ? lo : hi;
-    v[i] = keep + dpp_f64(give, SEL);
-  }
-}
+// Six half-exchange steps (m3s_common.hpp: swap_add<32>, swap_add<16>, then dpp_step by row_ror:8, row_half_mirror
+// and the two quad_perms). At every step a lane keeps one half of its current sums and adds the partner's copy of
+// that half. Afterwards lane gn_lane_of(c) holds the wave's total of sum c (the other 28 lanes hold padding zeros).
+// Fixed order: identical in every block and every run.
 
 // lane holding sum c after wave_sum36 (c < 36)
 __device__ __forceinline__ int gn_lane_of(int c) {
