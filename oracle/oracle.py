@@ -283,6 +283,17 @@ def pose_retr(Twc, dx, num_fix=1):
     return Twc
 
 
+def pose_retr_f64(Twc, dx, num_fix=1):
+    """``pose_retr`` in the fp64 truth build: float64 poses in, float64 poses out."""
+    Twc = np.array(Twc, np.float64, copy=True, order="C")
+    dx = _c(dx, np.float64)
+    fn = lib64().m3o_pose_retr
+    fn.argtypes = [_f64p, _f64p, ctypes.c_int, ctypes.c_int]
+    fn.restype = None
+    fn(_p(Twc, _f64p), _p(dx, _f64p), Twc.shape[0], num_fix)
+    return Twc
+
+
 def exp_sim3_f32(xi):
     xi = _c(xi, np.float32)
     out = np.zeros(8, np.float32)

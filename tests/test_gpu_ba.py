@@ -7,6 +7,7 @@ import pytest
 import torch
 
 import oracle.oracle as O
+from ba_solve_cases import host_solve_from_edge_sums as _host_solve_from_edge_sums
 
 pytestmark = pytest.mark.gpu
 
@@ -204,33 +205,6 @@ def test_single_keyframe_is_a_noop():
     T, dx = _call("rays", Twc0, Xs, np.full((1, N, 1), 2.0, np.float32), np.array([0]), np.array([0]),
                   np.zeros((1, N), np.int64), np.ones((1, N, 1), bool), np.full((1, N, 1), 2.0, np.float32), None, 0, 0)
     assert dx.shape == (0, 7) and np.array_equal(T, Twc0)
-
-
-def _host_solve_from_edge_sums(es, ii, jj):
-    """fp64 host assembly of the pose system from the (E,36) edge-sum table (the rule of
-    gn_kernels.cu:71-113 with pin 1: H_ii += M, H_ij = H_ji -= M, H_jj += M; g_i -= g, g_j += g)
-    and dx = -H^-1 g by numpy (LAPACK)."""
-    u = np.unique(np.concatenate((ii, jj)))
-    ri, rj = np.searchsorted(u, ii) - 1, np.searchsorted(u, jj) - 1
-    n = (len(u) - 1) * 7
-    Hs, g = np.zeros((n, n)), np.zeros(n)
-    iu = np.triu_indices(7)
-    for e in range(es.shape[0]):
-        M = np.zeros((7, 7))
-        M[iu] = es[e, :28]
-        M = M + np.triu(M, 1).T
-        gv = es[e, 28:35]
-        a, b = ri[e], rj[e]
-        if a >= 0:
-            Hs[7 * a:7 * a + 7, 7 * a:7 * a + 7] += M
-            g[7 * a:7 * a + 7] -= gv
-        if b >= 0:
-            Hs[7 * b:7 * b + 7, 7 * b:7 * b + 7] += M
-            g[7 * b:7 * b + 7] += gv
-        if a >= 0 and b >= 0:
-            Hs[7 * a:7 * a + 7, 7 * b:7 * b + 7] -= M
-            Hs[7 * b:7 * b + 7, 7 * a:7 * a + 7] -= M
-    return -np.linalg.solve(Hs, g)
 
 
 @pytest.mark.parametrize("solver", ["sparse", "dense"])
