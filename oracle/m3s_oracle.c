@@ -133,7 +133,7 @@ static inline void m3o_bilinear_weights(float u, float v, int* u11, int* v11, fl
 /* prep_for_iter_proj's torch glue (matching.py:25-49, image.py:5-38) in the reference's own fp32 */
 /* arithmetic. Pinned against the reference run (tests/golden/matching_48x64.npz rays / pts, bit  */
 /* for bit; tests/test_oracle.py): torch's CPU vector_norm of a 3-vector is the FMA chain          */
-/* sqrt(fma(z, z, fma(y, y, x * x))), F.normalize divides by max(norm, eps), and the depthwise     */
+/* sqrt(fma(z, z, fma(y, y, x * x))), F.normalize divides by norm.clamp_min(eps), and the depthwise */
 /* conv2d of the reflect-padded image is a row-major FMA chain over all 9 taps, zero taps included */
 /* (acc = w00 * v00, then acc = fma(w, v, acc)).                                                   */
 /* ------------------------------------------------------------------------------------------ */
@@ -147,7 +147,10 @@ void m3o_norm3(const float* x, float* out, int64_t n) {
 void m3o_normalize3(const float* x, float* out, int64_t n) {
 #pragma omp parallel for schedule(static)
   for (int64_t i = 0; i < n; i++) {
-    const float nr = fmaxf(m3o_norm3f(x[3 * i], x[3 * i + 1], x[3 * i + 2]), 1e-12f);
+    /* norm.clamp_min(eps): torch's clamp propagates a NaN norm (fmaxf would return eps), so a point with one NaN
+     * component normalises to three NaNs */
+    const float nr0 = m3o_norm3f(x[3 * i], x[3 * i + 1], x[3 * i + 2]);
+    const float nr = nr0 < 1e-12f ? 1e-12f : nr0;
     for (int c = 0; c < 3; c++) out[3 * i + c] = x[3 * i + c] / nr;
   }
 }

@@ -314,7 +314,8 @@ def norm3(x):
 
 
 def normalize(x, eps=1e-12):
-    """torch.nn.functional.normalize(x, dim=-1) of fp32 3-vectors: x / max(norm3(x), eps) in fp32."""
+    """torch.nn.functional.normalize(x, dim=-1) of fp32 3-vectors: x / norm3(x).clamp_min(eps) in fp32 (a NaN norm
+    stays NaN, as torch's clamp propagates it: tests/test_match_proj_host.py compares the two bit for bit)."""
     assert eps == 1e-12
     x = _c(x, np.float32)
     out = np.empty_like(x)
