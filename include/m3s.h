@@ -22,7 +22,7 @@
 extern "C" {
 #endif
 
-#define M3S_ABI_VERSION 9
+#define M3S_ABI_VERSION 10
 
 #define M3S_OK 0
 #define M3S_EINVAL -1  /* bad shape / argument (reference: TORCH_CHECK -> RuntimeError) */
@@ -39,7 +39,7 @@ const char* m3s_last_error(void);
  * with torch.cuda.synchronize). When enabled, every launch group is bracketed by hipEvents on its
  * own stream under a name: prep_rays, proj_occlusion, refine_lin, track_setup, gn_iters,
  * ba_linearize, ba_solve, map_count, map_voxel, map_write, quantize_topk, asmk_update (the whole fused call, the
- * quantiser's span inside it). query synchronises the recorded events. (m3s_match runs the
+ * quantiser's span inside it), rope2d. query synchronises the recorded events. (m3s_match runs the
  * projection search inside the refine launch where the tile path is taken: refine_lin then covers both and
  * proj_occlusion has no spans, count 0; M3S_MATCH_FUSE_PROJ=0 separates them.) */
 void m3s_timing_enable(int on);
@@ -176,6 +176,39 @@ int m3s_ba_pattern_stats(const int64_t* ii, const int64_t* jj, int E, int Kp, in
  * and height floats): x_of_u[u] = (float(u) - cx) / fx, y_of_v[v] = (float(v) - cy) / fy, each one fp32 subtraction
  * then one correctly rounded fp32 division (geometry.backproject's operation order; not a reciprocal-multiply). */
 int m3s_ba_calib_rays(const m3s_ba_config* cfg, float* x_of_u, float* y_of_v);
+
+/* curope.rope_2d(tokens, positions, base, fwd)              the reference's second native extension, the ViT's
+ *                                                           RoPE2D: croco/models/curope/curope.cpp:49-65 (binding
+ *                                                           and checks), kernels.cu:17-108 (kernel and launcher),
+ *                                                           curope2d.py:6-9 (`import curope`)
+ * tokens (B,N,H,D) f16 / f32 / bf16 (dtype 0 / 1 / 2), D % 4 == 0, Q = D / 4, rotated IN PLACE (as the reference).
+ * Element strides: stride_b and stride_n are arbitrary (the caller's q and k are views of the fused qkv buffer,
+ * blocks.py:99-105, token stride 3 H D); the head stride is D and the last 1 (kernels.cu:91). pos (B,N,2) i64
+ * contiguous, y then x. For axis a in {0, 1}, head h and t < Q, with u = tok[b,n,h, 2 a Q + t] and
+ * v = tok[b,n,h, 2 a Q + Q + t]: u' = u c - v s, v' = v c + u s, c, s = cos, sin(fwd pos[b,n,a] / base^(t/Q));
+ * fwd is F0, or -F0 in the backward pass of the reference's autograd function (curope2d.py:25-29).
+ * Numerics (the reference evaluates powf, cosf and sinf in fp32 in every thread, kernels.cu:44,52-54): c and s come
+ * from a table the library caches per (device, base, fwd, Q): for p in [0, 1024), host fp64
+ * inv = double(fwd) / pow(double(base), double(t) / Q), a = p inv, c = float(cos(a)), s = float(sin(a)), uploaded
+ * synchronously on first use. The kernel computes in fp32 exactly as written above, two products and one sum per
+ * output with no contraction, and rounds once (nearest even) to the token dtype. A position outside [0, 1024),
+ * negative ones included, takes the same formula in fp64 on the device (a = p inv[t], device cos / sin, rounded to
+ * fp32): the operator is total without a host look at the positions. f64 tokens have no dtype code (the reference
+ * computes them in float, and the ViT has none).
+ * 16-byte accesses are used when Q * sizeof(dtype) % 16 == 0 and tokens, stride_b and stride_n are 16-byte aligned;
+ * every other legal shape takes one element per lane. The launch is asynchronous on `stream`; B N H == 0 launches
+ * nothing. M3S_EINVAL: bad dtype, D % 4 != 0, a negative size, a null pointer with non-empty work, base not finite
+ * and positive.
+ * m3s_rope2d_prepare builds and uploads the table of (base, fwd, Q) on the current device if it is not cached: call
+ * it once before capturing m3s_rope2d into a graph (the first use of a table allocates and copies, which a capture
+ * forbids). m3s_rope2d_table is host-only, like m3s_ba_calib_rays: the host code that fills the device table writes
+ * its first P rows, P x Q floats each, to cos_out and sin_out (host). m3s_rope2d_release frees the current device's
+ * cached tables (after the device's pending work); a later call builds them again. */
+int m3s_rope2d(int dtype /* 0 f16, 1 f32, 2 bf16 */, void* tokens, int64_t stride_b, int64_t stride_n,
+               const int64_t* pos, int B, int N, int H, int D, float base, float fwd, void* stream);
+int m3s_rope2d_prepare(float base, float fwd, int Q, void* stream);
+int m3s_rope2d_table(float base, float fwd, int Q, int P, float* cos_out, float* sin_out);
+int m3s_rope2d_release(void);
 
 /* ---------------------------------------------------------------------------------------------
  * Fused operators (replace stretches of the reference's Python glue)

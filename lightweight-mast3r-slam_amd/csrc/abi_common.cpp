@@ -1,7 +1,7 @@
 // C ABI of libm3s.so (include/m3s.h), the part every subsystem shares: the last-error text, the per-kernel timing
 // spans, the pinned upload stage, the ABI version and the measured-peak probe. The subsystems' entry points (argument
 // validation, workspace carving, host-side planning and launch sequencing) live in abi_match.cpp, abi_track.cpp,
-// abi_ba.cpp, abi_retrieval.cpp and abi_map.cpp; the kernels in the .hip files. No torch types anywhere.
+// abi_ba.cpp, abi_retrieval.cpp, abi_map.cpp and abi_rope.cpp; the kernels in the .hip files. No torch types anywhere.
 #include "abi_common.h"
 
 #include <algorithm>

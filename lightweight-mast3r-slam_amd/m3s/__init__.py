@@ -2,8 +2,8 @@
 
 Modules: matching (fused dense matcher), tracker (FrameTracker), global_opt (FactorGraph),
 dist_ba (edge-sharded multi-GPU BA), evaluate (map and trajectory export), sim3 (lietorch-compatible Sim3),
-frame, config, synthetic.
-The drop-in operator module is the sibling package ``mast3r_slam_backends``.
+rope (the ViT's RoPE2D module), frame, config, synthetic.
+The drop-in operator modules are the sibling packages ``mast3r_slam_backends`` and ``curope``.
 """
 import os
 import sys

@@ -14,7 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # M3S_LIB: alternative build of the same library (kernel experiments); still the HIP library, no fallback
 LIB_PATH = os.environ.get("M3S_LIB") or os.path.join(os.path.dirname(_HERE), "lib", "libm3s.so")
 
-ABI_VERSION = 9  # include/m3s.h M3S_ABI_VERSION
+ABI_VERSION = 10  # include/m3s.h M3S_ABI_VERSION
 
 c_int, c_float, c_double, c_size_t, c_void_p = ctypes.c_int, ctypes.c_float, ctypes.c_double, ctypes.c_size_t, ctypes.c_void_p
 
@@ -136,6 +136,11 @@ _SIGS = {
     "m3s_map_voxel": ([ctypes.POINTER(MapConfig), ctypes.POINTER(BaKeyframes), c_void_p, c_int, c_int, c_float,
                        c_void_p, c_size_t, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64),
                        ctypes.POINTER(ctypes.c_int64), c_void_p, c_size_t, c_void_p], c_int),
+    "m3s_rope2d": ([c_int, c_void_p, ctypes.c_int64, ctypes.c_int64, c_void_p] + [c_int] * 4 + [c_float, c_float, c_void_p],
+                   c_int),
+    "m3s_rope2d_prepare": ([c_float, c_float, c_int, c_void_p], c_int),
+    "m3s_rope2d_table": ([c_float, c_float, c_int, c_int, c_void_p, c_void_p], c_int),
+    "m3s_rope2d_release": ([], c_int),
     "m3s_peak_fma_f32": ([c_void_p, c_int, c_int, c_void_p], c_int),
     "m3s_match_workspace_size": ([c_int] * 4, c_size_t),
     "m3s_match": ([c_void_p] * 7 + [c_int] * 5 + [c_float] * 3 + [c_int, c_int, c_void_p, c_size_t, c_void_p], c_int),
@@ -210,6 +215,19 @@ def ba_calib_rays(cfg):
     y = np.empty(int(cfg.height), dtype=np.float32)
     check(lib.m3s_ba_calib_rays(ctypes.byref(cfg), c_void_p(x.ctypes.data), c_void_p(y.ctypes.data)))
     return x, y
+
+
+def rope2d_table(base, fwd, Q, P=1024):
+    """Host-only: the (P, Q) float32 cos and sin tables of RoPE2D for (base, fwd, Q), from the host code that fills the
+    device table of m3s_rope2d: float32(cos / sin(p * (fwd / base ** (t / Q)))) evaluated in fp64."""
+    import numpy as np
+
+    lib = load(require_gpu=False)
+    cos = np.empty((int(P), int(Q)), dtype=np.float32)
+    sin = np.empty((int(P), int(Q)), dtype=np.float32)
+    check(lib.m3s_rope2d_table(float(base), float(fwd), int(Q), int(P), c_void_p(cos.ctypes.data),
+                               c_void_p(sin.ctypes.data)))
+    return cos, sin
 
 
 def check(rc):
