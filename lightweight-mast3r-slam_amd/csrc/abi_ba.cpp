@@ -1,7 +1,7 @@
 // C ABI of libm3s.so (include/m3s.h): bundle adjustment. The plan (rank remap, record reuse, linearisation table,
-// one upload), the symbolic worker (assembly pattern, factor schedule), and the linearise / solve entry points.
-// Kernels live in ba.hip (linearisation), ba_sparse.hip and ba_dense.hip (the solves), the pattern analysis in
-// ba_pattern.cpp.
+// one upload), the symbolic worker (its thread, generation and upload; what it computes is ba_build_plan), and the
+// linearise / solve entry points. Kernels live in ba.hip (linearisation), ba_sparse.hip and ba_dense.hip (the solves),
+// the pattern analysis and the plan's host-built half (the BA_SYM_SECTIONS image) in ba_pattern.cpp.
 #include "abi_common.h"
 
 #include <algorithm>
@@ -35,8 +35,6 @@ void m3s_abi::ba_calib_rays(const m3s_ba_config* cfg, float* x_of_u, float* y_of
 }
 
 namespace {
-
-constexpr int BA_MAX_WIDE_STEPS = 40;
 
 struct BaPlanImpl {
   BaArgs a;
@@ -78,9 +76,9 @@ inline size_t ba_max_blocks(int Kp) {
 }
 
 // the plan's host-built tables, uploaded in ONE copy: rank arrays, keyframe pointer tables and the
-// symbolic factorisation (ba_pattern.h), packed at their actual sizes into a region sized for the worst case
-constexpr int BA_SYM_SECTIONS = 16;  // the symbolic half's sections (build_symbolic)
-constexpr int BA_BLOB_SECTIONS = 9 + BA_SYM_SECTIONS;
+// symbolic factorisation (ba_pattern.h BA_SYM_SECTIONS), packed at their actual sizes into a region sized for the
+// worst case
+constexpr int BA_BLOB_SECTIONS = 9 + BA_SYM_NSEC;
 // update pairs (source block row -> target block) the plan can hold: every pattern up to K ~ 600, and the
 // sparse patterns of larger graphs
 inline size_t ba_max_pairs(int Kp) {
@@ -88,14 +86,11 @@ inline size_t ba_max_pairs(int Kp) {
   return std::min(nb * nb * nb / 6 + nb * nb + 64, 32 * ba_max_blocks(Kp) + 64);
 }
 size_t ba_blob_capacity(int Kp, int N, int E, int chunks) {
-  const size_t nb = (size_t)std::max(0, Kp - 1), nLm = ba_max_blocks(Kp);
-  // ranks, perm, col_ptr, rowL, lev_ptr, lev_col, grp_ptr, grp, pull_grp, src, sidx, asm CSR, rhs CSR
-  const size_t ints = 2 * (size_t)E + nb + (nb + 1) + nLm + (nb + 1) + nb + (nb + 2) + 4 * nLm + nb + 4 * nLm +
-                      ba_max_pairs(Kp) + (nLm + 1) + 4 * (size_t)E + (nb + 1) + 2 * (size_t)E +
-                      (size_t)E * chunks +  // + the linearisation block table
-                      2 * (size_t)E +       // + record slots and the pack list (record reuse)
-                      8 * 2 * nb * (size_t)std::min<size_t>(BA_MAX_WIDE_STEPS, nb + 1) +  // + wide-step task records
-                      2 * (M3S_BA_SP_WAVES + 1) + 2 * nb + 2 * (nb + nLm);  // + the dataflow schedule
+  const size_t nb = (size_t)std::max(0, Kp - 1);
+  const size_t ints = 2 * (size_t)E +       // the ranks
+                      (size_t)E * chunks +  // the linearisation block table
+                      2 * (size_t)E +       // record slots and the pack list (record reuse)
+                      ba_sym_capacity_ints(nb, ba_max_blocks(Kp), E, ba_max_pairs(Kp), M3S_BA_SP_WAVES);
   return ints * 4 + (size_t)Kp * (8 + 8 + 4) + ba_ray_tab_floats(N) * 4 + BA_BLOB_SECTIONS * 16;
 }
 
@@ -262,137 +257,35 @@ struct PlanSym {
   bool joined = false, uploaded = false;
   int rc = M3S_OK;
   std::string err;
-  // worker output (read by the main thread only after the join)
-  std::vector<char> image;  // the tables, packed at 16-B aligned offsets, as uploaded
-  size_t off[BA_SYM_SECTIONS] = {0};
-  int nb = 0, nlev = 0, nL = 0, wide_steps = 0, dense = 0, flow = 0, plan_lo_off = 0, plan_bytes = 0;
+  BaSymPlan plan;  // worker output (read by the main thread only after the join): ba_build_plan's
   bool pack_deferred = false;    // the plan's pack runs inside its first linearisation (set at plan time, under g_sym_mu)
-  int step_tasks[BA_MAX_WIDE_STEPS] = {0};
-  int step_base[BA_MAX_WIDE_STEPS] = {0};  // first task record of each wide step
-  int step_na[BA_MAX_WIDE_STEPS] = {0};    // its factor tasks (update groups follow)
   char* dst = nullptr;  // device destination (the blob region after the plan's own tables)
 };
 std::mutex g_sym_mu;
 std::map<const void*, std::unique_ptr<PlanSym>> g_sym;  // by workspace
 unsigned long long g_sym_gen = 0;
 
-// worker: ranks ri / rj (all E edges) -> the packed symbolic tables and the factor schedule
-int build_symbolic(PlanSym* Y, std::vector<int> ri, std::vector<int> rj, int E, int Kp, bool has_dense,
-                   size_t capacity) {
-  BaPattern S;
-  ba_build_pattern(ri.data(), rj.data(), E, Kp, &S, ba_max_pairs(Kp));
-  if (S.too_dense || S.sidx.size() > ba_max_pairs(Kp)) {
-    Y->err = "ba: factor pattern too dense for the plan tables";
-    return M3S_EINVAL;
-  }
-  // sparse or dense factorisation: measured on MI355X (scripts/ba_exp.py), the one-workgroup sparse
-  // factorisation costs ~3.8 us per elimination-tree level plus ~0.03 us per source-map entry (its
-  // update volume); the dense one ~2.7 us per pose (its pivot chain)
-  Y->dense = has_dense && 3.8 * S.nlev + 0.03 * (double)S.sidx.size() > 2.7 * S.nb;
-  const char* solver = getenv("M3S_BA_SOLVER");
-  if (solver) {  // tests and experiments: force one factorisation
-    if (!strcmp(solver, "sparse")) Y->dense = 0;
-    if (!strcmp(solver, "dense") && has_dense) Y->dense = 1;
-  }
-  // the leaf end of the elimination tree as multi-workgroup launches (steps [0, wide_steps)), the root end in the
-  // one-workgroup kernel, minimising the measured step costs (MI355X, C5/C4 graphs): a launch ~5.8 us per step, a
-  // step inside the workgroup ~3.7 us per round of M3S_BA_SP_WAVES waves (one wave per task). M3S_BA_WIDE=t (tests,
-  // experiments): every step up to the last one with more than t tasks. (Round 5's opt-in alternatives for this
-  // split, the subtree, frontal, supernodal and dense-top phases, measured slower or no faster and were removed in
-  // round 6; they are kept at git tag ba-solver-experiments-r5, DESIGN.md §4 BA.)
-  std::vector<int> tasks(S.nlev + 1);
-  for (int l = 0; l <= S.nlev; l++) {
-    const int na = l < S.nlev ? S.lev_ptr[l + 1] - S.lev_ptr[l] : 0;
-    tasks[l] = na + S.grp_ptr[l + 1] - S.grp_ptr[l];
-    if (l < BA_MAX_WIDE_STEPS) Y->step_tasks[l] = tasks[l];
-  }
-  const int lmax = std::min(S.nlev + 1, BA_MAX_WIDE_STEPS);
-  const bool flow_on = env_flag("M3S_BA_FLOW", true);  // M3S_BA_FLOW=0 (A/B experiments): level-synchronous loops
-  std::vector<int> sched;
-  // the loop tables col_ptr .. sidx (sections 1-9, 16-B aligned as packed below): with the schedule behind them, the
-  // plan bytes of the one-workgroup kernel's LDS rule (m3s_ba.h ba_sp_lds_bytes)
-  size_t table_bytes = 0;
-  {
-    const std::vector<int>* t[9] = {&S.col_ptr, &S.lev_ptr, &S.lev_col, &S.grp_ptr, &S.grp, &S.pull_grp, &S.src,
-                                    &S.sidx, &S.rowL};
-    for (const std::vector<int>* v : t) table_bytes += (sizeof(int) * v->size() + 15) & ~(size_t)15;
-  }
-  auto launch_cost_split = [&]() {  // launched wide steps: minimise the measured step costs
-    constexpr double kLaunchUs = 5.8, kRoundUs = 3.7;
-    std::vector<double> suffix(lmax + 1, 0.0);  // cost of steps [L, lmax) inside the workgroup
-    for (int l = lmax - 1; l >= 0; l--)
-      suffix[l] = suffix[l + 1] + kRoundUs * ((tasks[l] + M3S_BA_SP_WAVES - 1) / M3S_BA_SP_WAVES);
-    int best_L = 0;
-    double best = suffix[0];
-    for (int L = 1; L <= lmax; L++) {
-      const double c = kLaunchUs * L + suffix[L];
-      if (c < best) {
-        best = c;
-        best_L = L;
-      }
-    }
-    return best_L;
-  };
+// the plan options the environment sets (tests and experiments): M3S_BA_SOLVER=sparse|dense forces one factorisation,
+// M3S_BA_WIDE=t sets the wide split, M3S_BA_FLOW=0 (A/B experiments) the level-synchronous loops
+BaPlanOptions plan_options(int Kp, bool has_dense, size_t capacity) {
+  BaPlanOptions o;
+  o.has_dense = has_dense;
+  if (const char* solver = getenv("M3S_BA_SOLVER"))
+    o.solver = !strcmp(solver, "sparse") ? 1 : !strcmp(solver, "dense") ? 2 : 0;
   if (const char* w = getenv("M3S_BA_WIDE")) {
-    const int thr = atoi(w);
-    int last = -1;
-    for (int l = 0; l <= S.nlev; l++)
-      if (tasks[l] > thr) last = l;
-    Y->wide_steps = std::min(last + 1, BA_MAX_WIDE_STEPS);
-  } else {
-    Y->wide_steps = launch_cost_split();
+    o.wide_by_thr = true;
+    o.wide_thr = atoi(w);
   }
-  // the wide steps' task records (ba_sparse_step_kernel): per task {j, b0, b1, pull group or -1} and its group's
-  // source range, so a launched task starts with its column's own loads
-  std::vector<int> step_rec;
-  {
-    auto put = [&](int j, int g) {
-      const int* gq = g >= 0 ? &S.grp[4 * (size_t)g] : nullptr;
-      const int r[8] = {j, S.col_ptr[j], S.col_ptr[j + 1], g, gq ? gq[1] : 0, gq ? gq[2] : 0, 0, 0};
-      step_rec.insert(step_rec.end(), r, r + 8);
-    };
-    for (int l = 0; l < lmax; l++) {
-      Y->step_base[l] = (int)step_rec.size() / 8;
-      Y->step_na[l] = l < S.nlev ? S.lev_ptr[l + 1] - S.lev_ptr[l] : 0;
-      for (int c = l < S.nlev ? S.lev_ptr[l] : 0; c < (l < S.nlev ? S.lev_ptr[l + 1] : 0); c++)
-        put(S.lev_col[c], S.pull_grp[S.lev_col[c]]);
-      for (int t = S.grp_ptr[l]; t < S.grp_ptr[l + 1]; t++) put(S.grp[4 * (size_t)t], t);  // (none at step 0)
-      Y->step_tasks[l] = (int)step_rec.size() / 8 - Y->step_base[l];
-    }
-  }
-  // dataflow schedule of the one-workgroup part and the back substitution (ba_pattern.h)
-  if (flow_on) ba_flow_schedule(S, Y->wide_steps, M3S_BA_SP_WAVES, &sched);
-  Y->flow = sched.empty() ? 0 : 1;
-  // a schedule that does not fit the LDS instance: the kernel would run level-synchronously, so drop it (and say so)
-  const size_t flow_lds = m3s::ba_sp_lds_bytes(table_bytes + sizeof(int) * sched.size(), S.nb, true);
-  if (Y->flow && flow_lds > (size_t)m3s::SP_PLAN_BYTES) {
-    Y->flow = 0;
-    sched.clear();
-  }
-  const std::vector<int>* secs[BA_SYM_SECTIONS] = {&S.perm,    &S.col_ptr,  &S.rowL,    &S.lev_ptr,  &S.lev_col,
-                                                   &S.grp_ptr, &S.grp,      &S.pull_grp, &S.src,     &S.sidx,
-                                                   &sched,     &S.asm_ptr,  &S.asm_ent, &S.rhs_ptr, &S.rhs_ent,
-                                                   &step_rec};
-  size_t total = 0;
-  for (int k = 0; k < BA_SYM_SECTIONS; k++) {
-    Y->off[k] = total;
-    total += (sizeof(int) * secs[k]->size() + 15) & ~(size_t)15;
-  }
-  if (total > capacity) {
-    Y->err = "ba: factor pattern too dense for the plan tables";
-    return M3S_EINVAL;
-  }
-  Y->image.assign(total, 0);
-  for (int k = 0; k < BA_SYM_SECTIONS; k++)
-    if (!secs[k]->empty()) memcpy(Y->image.data() + Y->off[k], secs[k]->data(), sizeof(int) * secs[k]->size());
-  Y->nb = S.nb;
-  Y->nlev = S.nlev;
-  Y->nL = S.nL;
-  Y->plan_lo_off = (int)Y->off[1];  // col_ptr .. sidx and the dataflow schedule, staged into LDS by the factor kernel
-  Y->plan_bytes = (int)(Y->off[10] + sched.size() * sizeof(int) - Y->off[1]);
-  return M3S_OK;
+  o.flow = env_flag("M3S_BA_FLOW", true);
+  o.max_pairs = ba_max_pairs(Kp);
+  o.capacity = capacity;
+  return o;
 }
 
+// worker: ranks ri / rj (all E edges) -> the packed symbolic tables and the factor schedule
+int build_symbolic(PlanSym* Y, std::vector<int> ri, std::vector<int> rj, int E, int Kp, BaPlanOptions opt) {
+  return ba_build_plan(ri.data(), rj.data(), E, Kp, opt, &Y->plan, &Y->err) ? M3S_OK : M3S_EINVAL;
+}
 
 // the plan's PlanSym, joined (with `upload`, its tables enqueued on `s` the first time); nullptr + g_err on failure
 PlanSym* plan_symbolic(const BaPlanImpl* P, hipStream_t s, bool upload, int* rc) {
@@ -409,11 +302,11 @@ PlanSym* plan_symbolic(const BaPlanImpl* P, hipStream_t s, bool upload, int* rc)
   }
   if (upload && !Y->uploaded && Y->rc == M3S_OK) {
     Y->uploaded = true;
-    if (!Y->image.empty()) {
+    if (!Y->plan.image.empty()) {
       static const UploadNames names = {"ba symbolic upload", "ba symbolic upload", "ba symbolic upload"};
-      const UploadSec image = {Y->image.data(), Y->image.size(), nullptr};
+      const UploadSec image = {Y->plan.image.data(), Y->plan.image.size(), nullptr};
       if ((Y->rc = stage_upload(&image, 1, Y->dst, s, names)) != M3S_OK) Y->err = g_err;
-      std::vector<char>().swap(Y->image);
+      std::vector<char>().swap(Y->plan.image);
     }
   }
   if (Y->rc != M3S_OK) {
@@ -428,18 +321,16 @@ PlanSym* plan_symbolic(const BaPlanImpl* P, hipStream_t s, bool upload, int* rc)
 BaArgs with_symbolic(const BaPlanImpl* P, const PlanSym* Y) {
   BaArgs a = P->a;
   const char* d = Y->dst;
-  const void** dst[BA_SYM_SECTIONS] = {
-      (const void**)&a.perm,    (const void**)&a.col_ptr, (const void**)&a.rowL,    (const void**)&a.lev_ptr,
-      (const void**)&a.lev_col, (const void**)&a.grp_ptr, (const void**)&a.grp,     (const void**)&a.pull_grp,
-      (const void**)&a.src,     (const void**)&a.sidx,    (const void**)&a.sched,   (const void**)&a.asm_ptr,
-      (const void**)&a.asm_ent, (const void**)&a.rhs_ptr, (const void**)&a.rhs_ent, (const void**)&a.step_rec};
-  for (int k = 0; k < BA_SYM_SECTIONS; k++) *dst[k] = d + Y->off[k];
-  a.plan_lo = d + Y->plan_lo_off;
-  a.plan_bytes = Y->plan_bytes;
-  a.nb = Y->nb;
-  a.nlev = Y->nlev;
-  a.wide_steps = Y->wide_steps;
-  a.flow = Y->flow;
+  const BaSymPlan& S = Y->plan;
+#define BA_SEC_ARG(name, src, lds, cap) a.name = reinterpret_cast<decltype(a.name)>(d + S.off[BA_SEC_##name]);
+  BA_SYM_SECTIONS(BA_SEC_ARG)
+#undef BA_SEC_ARG
+  a.plan_lo = d + S.plan_lo_off;
+  a.plan_bytes = S.plan_bytes;
+  a.nb = S.nb;
+  a.nlev = S.nlev;
+  a.wide_steps = S.wide_steps;
+  a.flow = S.flow;
   return a;
 }
 
@@ -686,7 +577,7 @@ int PlanBuild::upload() {
       {ray_tab.data(), sizeof(float) * ray_tab.size(), (const void**)&P.a.ray_tab},
   };
   constexpr int nsec = sizeof(secs) / sizeof(secs[0]);
-  static_assert(nsec + BA_SYM_SECTIONS == BA_BLOB_SECTIONS, "blob sections");
+  static_assert(nsec + BA_SYM_NSEC == BA_BLOB_SECTIONS, "blob sections");
   total = upload_bytes(secs, nsec);
   capacity = ba_blob_capacity(Kp, N, E, chunks);
   if (total > capacity) return fail(M3S_EINVAL, "ba: plan tables exceed the workspace blob");
@@ -780,8 +671,8 @@ int PlanBuild::run() {
   if (int rc = pack_or_defer()) return rc;
   // the symbolic analysis of ALL E edges (every rank builds the identical system) runs on a host worker while
   // the device packs and linearises
-  Y->fut = std::async(std::launch::async, build_symbolic, Y, std::move(ri), std::move(rj), E, Kp, P.a.H != nullptr,
-                      capacity - total);
+  Y->fut = std::async(std::launch::async, build_symbolic, Y, std::move(ri), std::move(rj), E, Kp,
+                      plan_options(Kp, P.a.H != nullptr, capacity - total));
   memcpy(plan->opaque, &P, sizeof(P));
   return M3S_OK;
 }
@@ -890,10 +781,10 @@ extern "C" int m3s_ba_plan_info(const m3s_ba_plan* plan, int* info) {
   const PlanSym* Y = plan_symbolic(P, nullptr, false, &rc);  // joins the symbolic analysis
   if (Y == nullptr) return rc;
   info[0] = P->p.chunks;
-  info[1] = Y->nL;
-  info[2] = Y->nlev;
-  info[3] = Y->wide_steps;
-  info[4] = Y->dense;
+  info[1] = Y->plan.nL;
+  info[2] = Y->plan.nlev;
+  info[3] = Y->plan.wide_steps;
+  info[4] = Y->plan.dense;
   info[5] = P->n_targets;
   info[6] = P->e1 - P->e0;
   info[7] = P->Kp;
@@ -931,9 +822,8 @@ extern "C" int m3s_ba_solve(const m3s_ba_plan* plan, void* stream) {
   if (Y == nullptr) return rc;
   const BaArgs a = with_symbolic(P, Y);
   Span sp("ba_solve", s);
-  HIP_TRY(Y->dense ? m3s_launch_ba_solve_dense(&a, P->Kp, Y->nL, P->delta_thresh, s)
-                   : m3s_launch_ba_solve(&a, P->Kp, Y->nL, P->delta_thresh, Y->step_tasks, Y->step_base,
-                                         Y->step_na, s),
+  HIP_TRY(Y->plan.dense ? m3s_launch_ba_solve_dense(&a, P->Kp, Y->plan.nL, P->delta_thresh, s)
+                        : m3s_launch_ba_solve(&a, P->Kp, Y->plan.nL, P->delta_thresh, Y->plan.steps, s),
           "ba solve launch");
   return M3S_OK;
 }

@@ -1,10 +1,13 @@
-// Symbolic analysis of the BA pose system: ordering, factor pattern, level schedule, assembly CSR.
-// See ba_pattern.h. Pure host C++ (runs once per BA plan).
+// Symbolic analysis of the BA pose system: ordering, factor pattern, level schedule, assembly CSR (ba_build_pattern),
+// the dataflow schedule (ba_flow_schedule), and the plan built from them: solver choice, wide split, task records and
+// the packed image of the BA_SYM_SECTIONS list (ba_build_plan). See ba_pattern.h. Pure host C++, no HIP (runs once per
+// BA plan; scripts/ba_flow_check.cpp checks it from a plain host program).
 #include "ba_pattern.h"
 
 #include <algorithm>
 #include <climits>
 #include <cstdint>
+#include <cstring>
 #include <utility>
 
 namespace {
@@ -335,12 +338,10 @@ double ba_flow_schedule(const BaPattern& P, int wide, int waves, std::vector<int
     bwave[j] = B.place(deps, 0.7 + 0.02 * (P.col_ptr[j + 1] - P.col_ptr[j]));
   }
   const int nt = (int)tasks.size();
-  sched->assign(2 * (waves + 1) + nb + 2 * (size_t)nt + bcol.size(), 0);
-  int* wl_ptr = sched->data();
-  int* bs_ptr = wl_ptr + waves + 1;
-  int* fac_init = bs_ptr + waves + 1;
-  int* wl_task = fac_init + nb;
-  int* bs_col = wl_task + 2 * (size_t)nt;
+  sched->assign(BaFlowView::ints(waves, nb, nt), 0);
+  const BaFlowViewT<int> V{sched->data(), waves, nb};
+  V.wl_ptr()[waves] = nt;  // (bs_col sits behind the nt tasks)
+  int *wl_ptr = V.wl_ptr(), *bs_ptr = V.bs_ptr(), *fac_init = V.fac_init(), *wl_task = V.wl_task(), *bs_col = V.bs_col();
   for (int k = 0; k < nb; k++) fac_init[k] = lev[k] < done_below ? 1 : 0;
   for (int w = 0, o = 0, ob = 0; w < waves; w++) {
     wl_ptr[w] = o;
@@ -365,5 +366,112 @@ double ba_flow_schedule(const BaPattern& P, int wide, int waves, std::vector<int
     bs_ptr[w + 1] = ob;
   }
   return makespan;
+}
+
+namespace {
+inline size_t pad16(size_t ints) { return (sizeof(int) * ints + 15) & ~(size_t)15; }
+
+// launched wide steps [0, L) of the lmax candidates: minimise the measured step costs (MI355X, C5/C4 graphs): a
+// launch ~5.8 us per step, a step inside the workgroup ~3.7 us per round of M3S_BA_SP_WAVES waves (one wave per task)
+int launch_cost_split(const std::vector<int>& tasks, int lmax) {
+  constexpr double kLaunchUs = 5.8, kRoundUs = 3.7;
+  std::vector<double> suffix(lmax + 1, 0.0);  // cost of steps [L, lmax) inside the workgroup
+  for (int l = lmax - 1; l >= 0; l--)
+    suffix[l] = suffix[l + 1] + kRoundUs * ((tasks[l] + M3S_BA_SP_WAVES - 1) / M3S_BA_SP_WAVES);
+  int best_L = 0;
+  double best = suffix[0];
+  for (int L = 1; L <= lmax; L++) {
+    const double c = kLaunchUs * L + suffix[L];
+    if (c < best) {
+      best = c;
+      best_L = L;
+    }
+  }
+  return best_L;
+}
+}  // namespace
+
+bool ba_build_plan(const int* ri, const int* rj, int E, int Kp, const BaPlanOptions& opt, BaSymPlan* Y,
+                   std::string* err, BaPlanSources* keep) {
+  BaPlanSources local;
+  BaPlanSources& Q = keep ? *keep : local;
+  BaPattern& S = Q.S;
+  ba_build_pattern(ri, rj, E, Kp, &S, opt.max_pairs);
+  if (S.too_dense || S.sidx.size() > opt.max_pairs) {
+    *err = "ba: factor pattern too dense for the plan tables";
+    return false;
+  }
+  // sparse or dense factorisation: measured on MI355X (scripts/ba_exp.py), the one-workgroup sparse
+  // factorisation costs ~3.8 us per elimination-tree level plus ~0.03 us per source-map entry (its
+  // update volume); the dense one ~2.7 us per pose (its pivot chain)
+  Y->dense = opt.has_dense && 3.8 * S.nlev + 0.03 * (double)S.sidx.size() > 2.7 * S.nb;
+  if (opt.solver == 1) Y->dense = 0;  // tests and experiments: force one factorisation
+  if (opt.solver == 2 && opt.has_dense) Y->dense = 1;
+  // the leaf end of the elimination tree as multi-workgroup launches (steps [0, wide_steps)), the root end in the
+  // one-workgroup kernel (launch_cost_split), or by opt.wide_thr = t (tests, experiments): every step up to the last
+  // one with more than t tasks. (Round 5's opt-in alternatives for this split, the subtree, frontal, supernodal and
+  // dense-top phases, measured slower or no faster and were removed in round 6; they are kept at git tag
+  // ba-solver-experiments-r5, DESIGN.md §4 BA.)
+  // Per step its task records: the level's factor tasks, then the update groups of the level below (none at step 0)
+  const int lmax = std::min(S.nlev + 1, BA_MAX_WIDE_STEPS);
+  std::vector<int> tasks(S.nlev + 1);
+  std::vector<BaStepRec> recs;
+  for (int l = 0; l <= S.nlev; l++) {
+    const int c0 = l < S.nlev ? S.lev_ptr[l] : 0, c1 = l < S.nlev ? S.lev_ptr[l + 1] : 0;
+    tasks[l] = c1 - c0 + S.grp_ptr[l + 1] - S.grp_ptr[l];
+    if (l >= lmax) continue;
+    Y->steps[l] = BaWideStep{(int)recs.size(), c1 - c0, tasks[l]};
+    for (int c = c0; c < c1; c++) recs.push_back(ba_step_rec(S, S.lev_col[c], S.pull_grp[S.lev_col[c]]));
+    for (int t = S.grp_ptr[l]; t < S.grp_ptr[l + 1]; t++) recs.push_back(ba_step_rec(S, S.grp[4 * (size_t)t], t));
+  }
+  Q.step_rec.resize(recs.size() * (sizeof(BaStepRec) / sizeof(int)));
+  if (!recs.empty()) memcpy(Q.step_rec.data(), recs.data(), sizeof(BaStepRec) * recs.size());
+  if (opt.wide_by_thr) {
+    int last = -1;
+    for (int l = 0; l <= S.nlev; l++)
+      if (tasks[l] > opt.wide_thr) last = l;
+    Y->wide_steps = std::min(last + 1, BA_MAX_WIDE_STEPS);
+  } else {
+    Y->wide_steps = launch_cost_split(tasks, lmax);
+  }
+  const std::vector<int>* secs[BA_SYM_NSEC] = {
+#define BA_SEC_SRC(name, src, lds, cap) &Q.src,
+      BA_SYM_SECTIONS(BA_SEC_SRC)
+#undef BA_SEC_SRC
+  };
+  static const bool lds[BA_SYM_NSEC] = {
+#define BA_SEC_LDS(name, src, lds, cap) lds != 0,
+      BA_SYM_SECTIONS(BA_SEC_LDS)
+#undef BA_SEC_LDS
+  };
+  // dataflow schedule of the one-workgroup part and the back substitution. One that does not fit the LDS instance
+  // beside the other LDS-staged sections: the kernel would run level-synchronously, so drop it
+  size_t table_bytes = 0;  // (the schedule's own section is still empty here)
+  for (int k = 0; k < BA_SYM_NSEC; k++) table_bytes += lds[k] ? pad16(secs[k]->size()) : 0;
+  if (opt.flow) ba_flow_schedule(S, Y->wide_steps, M3S_BA_SP_WAVES, &Q.sched);
+  if (m3s::ba_sp_lds_bytes(table_bytes + sizeof(int) * Q.sched.size(), S.nb, true) > (size_t)m3s::SP_PLAN_BYTES)
+    Q.sched.clear();
+  Y->flow = Q.sched.empty() ? 0 : 1;
+  size_t total = 0;
+  int lds_first = -1, lds_last = -1;
+  for (int k = 0; k < BA_SYM_NSEC; k++) {
+    Y->off[k] = total;
+    total += pad16(secs[k]->size());
+    if (lds[k]) lds_last = k;
+    if (lds[k] && lds_first < 0) lds_first = k;
+  }
+  if (total > opt.capacity) {
+    *err = "ba: factor pattern too dense for the plan tables";
+    return false;
+  }
+  Y->image.assign(total, 0);
+  for (int k = 0; k < BA_SYM_NSEC; k++)
+    if (!secs[k]->empty()) memcpy(Y->image.data() + Y->off[k], secs[k]->data(), sizeof(int) * secs[k]->size());
+  Y->nb = S.nb;
+  Y->nlev = S.nlev;
+  Y->nL = S.nL;
+  Y->plan_lo_off = (int)Y->off[lds_first];
+  Y->plan_bytes = (int)(Y->off[lds_last] + sizeof(int) * secs[lds_last]->size() - Y->off[lds_first]);
+  return true;
 }
 

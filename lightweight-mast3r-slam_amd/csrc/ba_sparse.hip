@@ -22,9 +22,13 @@
 // Then the back substitution x_j = L_jj^-T (y_j - sum_i L_ij^T x_i), levels from the root down; then
 // dx = -x in pose order (0 on a failed pivot: the reference's silent zero step), the Sim(3) retraction
 // and the |dx| early exit on the device: no host synchronisation inside the GN loop.
+// The kernel body is a sequence of parts: sp_stage_tables, sp_init_flags, then either the dataflow schedule
+// (sp_flow_factor, sp_flow_back: per-wave task lists, flags instead of barriers) or the level-synchronous loops
+// (sp_level_factor, sp_level_back), then sp_finish. Both schedules run the same per-task code (sp_column_task,
+// sp_back_column), as do the launched wide steps (ba_sparse_step_kernel): the factor is bit-identical across them.
 #include "m3s_ba.h"  // the launchers defined here
 #include "m3s_ba_dev.hpp"
-#include "ba_pattern.h"  // BA_BS_* flags of the dataflow back-substitution lists
+#include "ba_pattern.h"  // the host-built half of the plan: BaFlowView (the schedule's layout), BaStepRec, BA_BS_* flags
 #include <cstring>
 
 namespace m3s {
@@ -71,46 +75,27 @@ __device__ unsigned long long g_sp_stamps[4096];
     if (lane == 0 && (k) < 2000) g_sp_stamps[1000 + (k)] = __builtin_amdgcn_s_memrealtime(); \
   } while (0)
 #else
-#define TST(k) \
-  do {         \
-  } while (0)
-#define SPST(k) \
-  do {          \
-  } while (0)
-#define FST(k) \
-  do {         \
-  } while (0)
+#define TST(k) ((void)0)
+#define SPST(k) ((void)0)
+#define FST(k) ((void)0)
 #endif
 
-// the plan's loop tables (LDS when they fit)
+// the plan's loop tables: the LDS-staged sections of BA_SYM_SECTIONS (ba_pattern.h), typed as in BaArgs
 struct SpTables {
-  const int* col_ptr;
-  const int* rowL;
-  const int* lev_ptr;
-  const int* lev_col;
-  const int* grp_ptr;
-  const int4* grp;
-  const int* pull_grp;
-  const int4* src;
-  const int* sidx;
-  const int* sched;
+#define SP_MEMBER(name, src, lds, cap) decltype(BaArgs::name) name;
+  BA_SYM_SECTIONS(SP_MEMBER)  // (only the LDS-staged ones are set and read)
+#undef SP_MEMBER
 };
 
 // the loop tables at `base`: the plan's table region [plan_lo, plan_lo + plan_bytes) staged to `base` (LDS), or
 // base = plan_lo itself (global)
 __device__ __forceinline__ SpTables sp_tables(const BaArgs& a, const int* base) {
   const int* g = reinterpret_cast<const int*>(a.plan_lo);
-  SpTables T;
-  T.col_ptr = base + (a.col_ptr - g);
-  T.rowL = base + (a.rowL - g);
-  T.lev_ptr = base + (a.lev_ptr - g);
-  T.lev_col = base + (a.lev_col - g);
-  T.grp_ptr = base + (a.grp_ptr - g);
-  T.grp = reinterpret_cast<const int4*>(base + (reinterpret_cast<const int*>(a.grp) - g));
-  T.pull_grp = base + (a.pull_grp - g);
-  T.src = reinterpret_cast<const int4*>(base + (reinterpret_cast<const int*>(a.src) - g));
-  T.sidx = base + (a.sidx - g);
-  T.sched = base + (a.sched - g);
+  SpTables T = {};
+#define SP_REBASE(name, src, lds, cap) \
+  if (lds) T.name = reinterpret_cast<decltype(T.name)>(base + (reinterpret_cast<const int*>(a.name) - g));
+  BA_SYM_SECTIONS(SP_REBASE)
+#undef SP_REBASE
   return T;
 }
 
@@ -132,9 +117,9 @@ __device__ __forceinline__ SpTask sp_task_of_group(const SpTables& T, int g) {
   const int4 gq = T.grp[g];
   return SpTask{gq.x, T.col_ptr[gq.x], T.col_ptr[gq.x + 1], true, make_int2(gq.y, gq.z)};
 }
-// {j, b0, b1, pull group or -1}, {src begin, end, 0, 0} (abi_ba.cpp build_symbolic)
-__device__ __forceinline__ SpTask sp_task_of_record(const int4& r0, const int4& r1) {
-  return SpTask{r0.x, r0.y, r0.z, r0.w >= 0, make_int2(r1.x, r1.y)};
+// the host's restatement of the two above for a launched task (ba_pattern.h ba_step_rec)
+__device__ __forceinline__ SpTask sp_task_of_record(const BaStepRec& r) {
+  return SpTask{r.j, r.b0, r.b1, r.g >= 0, make_int2(r.src0, r.src1)};
 }
 
 // the rows of a column: row p < 7 (noff + 1) is row p % 7 of the column's block p / 7 (block 0 = the
@@ -168,6 +153,16 @@ __device__ __forceinline__ double sp_ljk(const BaArgs& a, int blk, int lane) {
   return lane < 49 ? a.L[(size_t)blk * 64 + (lane / 7) * 8 + lane - 7 * (lane / 7)] : 0.0;
 }
 
+// one source's step on a held row: the lane's element bv of L_jk into the wave's LDS row bjk (once the previous
+// source's reads of it are done), then v -= x L_jk^T where struct(k) has the row (s != nullptr)
+__device__ __forceinline__ void sp_stage_apply(double* bjk, double bv, int lane, const double* s, double (&v)[8],
+                                               const double (&x)[8]) {
+  wave_sync();
+  if (lane < 49) bjk[lane] = bv;
+  wave_sync();
+  if (s) sp_apply(v, x, bjk);
+}
+
 // apply the sources of group range gr to the rows p1 = lane and p2 = lane + 64 of column j held in v1 / v2
 // (rows beyond nrow are idle). Columns of at most 64 rows (the common case) issue the next source's
 // loads before the current one is applied.
@@ -191,10 +186,7 @@ __device__ __forceinline__ void sp_group_regs(const BaArgs& a, const SpTables& T
         nbv = sp_ljk(a, nl.x, lane);
         if (n1) ld_row(y1, n1);
       }
-      wave_sync();  // the previous source's reads of bjk are done
-      if (lane < 49) bjk[lane] = bv;
-      wave_sync();
-      if (s1) sp_apply(v1, x1, bjk);
+      sp_stage_apply(bjk, bv, lane, s1, v1, x1);
       s1 = n1;
       bv = nbv;
 #pragma unroll
@@ -209,10 +201,7 @@ __device__ __forceinline__ void sp_group_regs(const BaArgs& a, const SpTables& T
       double x1[8], x2[8];
       if (s1) ld_row(x1, s1);
       if (s2) ld_row(x2, s2);
-      wave_sync();
-      if (lane < 49) bjk[lane] = bv;
-      wave_sync();
-      if (s1) sp_apply(v1, x1, bjk);
+      sp_stage_apply(bjk, bv, lane, s1, v1, x1);
       if (s2) sp_apply(v2, x2, bjk);
     }
   }
@@ -236,10 +225,7 @@ __device__ __forceinline__ void sp_rows_extra(const BaArgs& a, const SpTables& T
         const double* sp = act ? sp_src_addr(a, T, pl, noff, p) : nullptr;
         double x[8];
         if (sp) ld_row(x, sp);
-        wave_sync();
-        if (lane < 49) bjk[lane] = bv;
-        wave_sync();
-        if (sp) sp_apply(v, x, bjk);
+        sp_stage_apply(bjk, bv, lane, sp, v, x);
       }
       wave_sync();
     }
@@ -450,11 +436,125 @@ __global__ void __launch_bounds__(64) ba_sparse_step_kernel(BaArgs a, int rec_ba
   // step and the one-workgroup kernel share one XCD's L2
   if (xcd_stride > 1 && blockIdx.x % xcd_stride != 0) return;
   const int task = blockIdx.x / xcd_stride;
-  const int4 r0 = a.step_rec[2 * (rec_base + task)], r1 = a.step_rec[2 * (rec_base + task) + 1];
+  const BaStepRec r = a.step_rec[rec_base + task];
   if (*a.done) return;
   const SpTables T = sp_tables(a, reinterpret_cast<const int*>(a.plan_lo));
-  if (task < na) sp_column_task<true>(a, T, sp_task_of_record(r0, r1), lane, s_red, a.bad);
-  else sp_column_task<false>(a, T, sp_task_of_record(r0, r1), lane, s_red, a.bad);
+  if (task < na) sp_column_task<true>(a, T, sp_task_of_record(r), lane, s_red, a.bad);
+  else sp_column_task<false>(a, T, sp_task_of_record(r), lane, s_red, a.bad);
+}
+
+// ---- ba_sparse_factor_kernel in parts: each is called once, in this order, by every thread of the workgroup ----
+
+// the plan's LDS-staged sections [plan_lo, plan_lo + plan_bytes) into s_plan: every thread's loads in flight at once
+__device__ __forceinline__ void sp_stage_tables(const BaArgs& a, int* s_plan) {
+  const int4* src = reinterpret_cast<const int4*>(a.plan_lo);
+  int4* dst = reinterpret_cast<int4*>(s_plan);
+  const int n16 = (a.plan_bytes + 15) / 16;
+  int4 tmp[8];
+  for (int i0 = 0; i0 < n16; i0 += 8 * 1024) {
+#pragma unroll
+    for (int u = 0; u < 8; u++) tmp[u] = src[min(i0 + u * 1024 + (int)threadIdx.x, n16 - 1)];
+#pragma unroll
+    for (int u = 0; u < 8; u++) {
+      const int i = i0 + u * 1024 + (int)threadIdx.x;
+      if (i < n16) dst[i] = tmp[u];
+    }
+  }
+}
+
+// the dataflow flags (LDS, after x), one word per column each
+struct SpFlags {
+  int* app;  // update groups landed on the column
+  int* fac;  // the column is factored
+  int* xd;   // its x is solved
+};
+// fac starts from the global schedule's fac_init (the staged copy is not visible before the barrier that follows)
+__device__ __forceinline__ void sp_init_flags(const BaArgs& a, const SpFlags& F, int nb) {
+  const int* fac_init = BaFlowView{a.sched, SP_WAVES, nb}.fac_init();
+  for (int i = threadIdx.x; i < nb; i += 1024) {
+    F.app[i] = 0;
+    F.fac[i] = fac_init[i];
+    F.xd[i] = 0;
+  }
+}
+
+// dataflow factor walk: wave w walks its own task list (step order); a task waits only for its inputs
+__device__ __forceinline__ void sp_flow_factor(const BaArgs& a, const SpTables& T, const BaFlowView& S,
+                                               const SpFlags& F, int w, int lane, double* red, int* bad) {
+  const int2* wl = reinterpret_cast<const int2*>(S.wl_task());
+  for (int t = S.wl_ptr()[w]; t < S.wl_ptr()[w + 1]; t++) {
+    const int2 tk = wl[t];  // {column j, or -1 - update group; the count of groups j took before this task}
+    if (tk.x >= 0) {
+      const SpTask k = sp_task_of_column(T, tk.x);
+      flow_wait_task(T, k.gr, F.fac, &F.app[k.j], tk.y, lane, bad, a.force_stall);
+      TST(2 * t);
+      sp_column_task<true>(a, T, k, lane, red, bad);
+      if (lane == 0) flow_st(&F.fac[k.j], 1);
+    } else {
+      const SpTask k = sp_task_of_group(T, -1 - tk.x);
+      flow_wait_task(T, k.gr, F.fac, &F.app[k.j], tk.y, lane, bad, a.force_stall);
+      TST(2 * t);
+      sp_column_task<false>(a, T, k, lane, red, bad);
+      if (lane == 0) flow_st(&F.app[k.j], tk.y + 1);
+    }
+    TST(2 * t + 1);
+    wave_sync();
+  }
+}
+
+// dataflow back substitution: wave w's columns, parents first, each waiting on the x-done flags of its struct
+__device__ __forceinline__ void sp_flow_back(const BaArgs& a, const SpTables& T, const BaFlowView& S, double* X,
+                                             const SpFlags& F, int w, int lane, double* red, int* bad) {
+  const int* bs_col = S.bs_col();
+  for (int t = S.bs_ptr()[w]; t < S.bs_ptr()[w + 1]; t++) {
+    const int code = bs_col[t];
+    sp_back_column(a, T, X, F.xd, code & BA_BS_COL, (code & BA_BS_NOWAIT) == 0, lane, red, bad);
+    FST(t);
+  }
+}
+
+// level-synchronous factor, steps [wide_steps, nlev]. Step l: factor the columns of level l (each pulls its
+// children's-level updates first) beside the push updates of level l-1 into the columns above level l; a barrier
+// ends every step
+__device__ __forceinline__ void sp_level_factor(const BaArgs& a, const SpTables& T, int w, int lane, double* red,
+                                                int* bad) {
+  const int nlev = a.nlev;
+  for (int l = a.wide_steps; l <= nlev; l++) {
+    const int c0 = l < nlev ? T.lev_ptr[l] : 0, na = l < nlev ? T.lev_ptr[l + 1] - c0 : 0;
+    const int t0 = T.grp_ptr[l], nt = T.grp_ptr[l + 1] - t0;
+    for (int task = w; task < na + nt; task += SP_WAVES) {
+      if (task < na) sp_column_task<true>(a, T, sp_task_of_column(T, T.lev_col[c0 + task]), lane, red, bad);
+      else sp_column_task<false>(a, T, sp_task_of_group(T, t0 + task - na), lane, red, bad);
+    }
+    __syncthreads();
+    SPST(2 + l);
+  }
+}
+
+// level-synchronous back substitution, levels from the root down; runs of single-column levels stay on wave 0 with
+// no barrier between them (LT, X in LDS: a wave's LDS accesses are ordered)
+template <bool LT>
+__device__ __forceinline__ void sp_level_back(const BaArgs& a, const SpTables& T, double* X, int w, int lane,
+                                              double* red, int* bad) {
+  const int nlev = a.nlev;
+  for (int l = nlev - 1; l >= 0; l--) {
+    const int c0 = T.lev_ptr[l], c1 = T.lev_ptr[l + 1];
+    for (int c = c0 + w; c < c1; c += SP_WAVES) sp_back_column(a, T, X, nullptr, T.lev_col[c], false, lane, red, bad);
+    const bool chain = LT && c1 - c0 == 1 && l > 0 && T.lev_ptr[l] - T.lev_ptr[l - 1] == 1;
+    if (!chain) {
+      __syncthreads();
+      SPST(3 + nlev + (nlev - 1 - l));
+    }
+  }
+}
+
+// dx = -x in pose order (0 on a failed pivot or a stall), the retraction and the early exit; the multi-workgroup
+// factor launches (the wide steps) report through *a.bad
+__device__ __forceinline__ void sp_finish(const BaArgs& a, const double* X, int K, float delta_thresh, int bad) {
+  const int ext_bad = a.wide_steps > 0 ? *(volatile int*)a.bad : 0;
+  const bool failed = bad != 0 || ext_bad != 0;
+  ba_finish_step<8>(a, X, K, delta_thresh, failed, ((bad | ext_bad) & BA_BAD_STALL) != 0);
+  if (threadIdx.x == 0) *a.info = failed ? 1 : 0;
 }
 
 template <bool LT>  // LT: the loop tables and x fit in LDS (index lookups are ds_reads), else global
@@ -465,108 +565,31 @@ __global__ void __launch_bounds__(1024) ba_sparse_factor_kernel(BaArgs a, int K,
   __shared__ int s_bad;
   const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
   SPST(0);
-  const int* g = reinterpret_cast<const int*>(a.plan_lo);
-  const int xoff = ((a.plan_bytes + 15) & ~15) / 4;  // ints
-  if constexpr (LT) {  // the loop tables into LDS: every thread's loads in flight at once
-    const int4* src = reinterpret_cast<const int4*>(a.plan_lo);
-    int4* dst = reinterpret_cast<int4*>(s_plan);
-    const int n16 = (a.plan_bytes + 15) / 16;
-    int4 tmp[8];
-    for (int i0 = 0; i0 < n16; i0 += 8 * 1024) {
-#pragma unroll
-      for (int u = 0; u < 8; u++) tmp[u] = src[min(i0 + u * 1024 + (int)threadIdx.x, n16 - 1)];
-#pragma unroll
-      for (int u = 0; u < 8; u++) {
-        const int i = i0 + u * 1024 + (int)threadIdx.x;
-        if (i < n16) dst[i] = tmp[u];
-      }
-    }
-  }
-  const int* base = LT ? static_cast<const int*>(s_plan) : g;
+  if constexpr (LT) sp_stage_tables(a, s_plan);
+  const int xoff = ((a.plan_bytes + 15) & ~15) / 4;  // ints: x follows the tables, the flags follow x
   double* X = LT ? reinterpret_cast<double*>(s_plan + xoff) : a.xs;
-  const SpTables T = sp_tables(a, base);
+  const SpTables T = sp_tables(a, LT ? static_cast<const int*>(s_plan) : reinterpret_cast<const int*>(a.plan_lo));
   const int nb = a.nb;
-  // dataflow flags after x: update groups landed per column, factored per column, x done per column
-  int* f_app = s_plan + xoff + 16 * nb;
-  int* f_fac = f_app + nb;
-  int* f_xd = f_fac + nb;
+  const SpFlags F = {s_plan + xoff + 16 * nb, s_plan + xoff + 17 * nb, s_plan + xoff + 18 * nb};
   const bool flow = LT && a.flow;
-  if (flow) {
-    const int* fac_init = a.sched + 2 * (SP_WAVES + 1);
-    for (int i = threadIdx.x; i < nb; i += 1024) {
-      f_app[i] = 0;
-      f_fac[i] = fac_init[i];
-      f_xd[i] = 0;
-    }
-  }
+  if (flow) sp_init_flags(a, F, nb);
   if (threadIdx.x == 0) s_bad = 0;
   __syncthreads();
   SPST(1);
-  const int nlev = a.nlev;
   if (flow) {
-    // every wave walks its own task list (step order); a task waits only for its inputs
-    const int* S = T.sched;
-    const int2* wl = reinterpret_cast<const int2*>(S + 2 * (SP_WAVES + 1) + nb);
-    for (int t = S[w]; t < S[w + 1]; t++) {
-      const int2 tk = wl[t];  // {column j, or -1 - update group; the count of groups j took before this task}
-      if (tk.x >= 0) {
-        const SpTask k = sp_task_of_column(T, tk.x);
-        flow_wait_task(T, k.gr, f_fac, &f_app[k.j], tk.y, lane, &s_bad, a.force_stall);
-        TST(2 * t);
-        sp_column_task<true>(a, T, k, lane, s_red[w], &s_bad);
-        if (lane == 0) flow_st(&f_fac[k.j], 1);
-      } else {
-        const SpTask k = sp_task_of_group(T, -1 - tk.x);
-        flow_wait_task(T, k.gr, f_fac, &f_app[k.j], tk.y, lane, &s_bad, a.force_stall);
-        TST(2 * t);
-        sp_column_task<false>(a, T, k, lane, s_red[w], &s_bad);
-        if (lane == 0) flow_st(&f_app[k.j], tk.y + 1);
-      }
-      TST(2 * t + 1);
-      wave_sync();
-    }
+    const BaFlowView S{T.sched, SP_WAVES, nb};
+    sp_flow_factor(a, T, S, F, w, lane, s_red[w], &s_bad);
     __syncthreads();
-    SPST(2 + nlev);
-    const int* bs_ptr = S + SP_WAVES + 1;
-    const int* bs_col = S + 2 * (SP_WAVES + 1) + nb + 2 * S[SP_WAVES];
-    for (int t = bs_ptr[w]; t < bs_ptr[w + 1]; t++) {
-      const int code = bs_col[t];
-      sp_back_column(a, T, X, f_xd, code & BA_BS_COL, (code & BA_BS_NOWAIT) == 0, lane, s_red[w], &s_bad);
-      FST(t);
-    }
-  }
-  // step l: factor the columns of level l (each pulls its children's-level updates first) beside the
-  // push updates of level l-1 into the columns above level l
-  for (int l = flow ? nlev + 1 : a.wide_steps; l <= nlev; l++) {
-    const int c0 = l < nlev ? T.lev_ptr[l] : 0, na = l < nlev ? T.lev_ptr[l + 1] - c0 : 0;
-    const int t0 = T.grp_ptr[l], nt = T.grp_ptr[l + 1] - t0;
-    for (int task = w; task < na + nt; task += SP_WAVES) {
-      if (task < na) sp_column_task<true>(a, T, sp_task_of_column(T, T.lev_col[c0 + task]), lane, s_red[w], &s_bad);
-      else sp_column_task<false>(a, T, sp_task_of_group(T, t0 + task - na), lane, s_red[w], &s_bad);
-    }
-    __syncthreads();
-    SPST(2 + l);
-  }
-  // back substitution, levels from the root down; runs of single-column levels stay on wave 0 with no
-  // barrier between them (X in LDS: a wave's LDS accesses are ordered)
-  for (int l = flow ? -1 : nlev - 1; l >= 0; l--) {
-    const int c0 = T.lev_ptr[l], c1 = T.lev_ptr[l + 1];
-    for (int c = c0 + w; c < c1; c += SP_WAVES)
-      sp_back_column(a, T, X, nullptr, T.lev_col[c], false, lane, s_red[w], &s_bad);
-    const bool chain = LT && c1 - c0 == 1 && l > 0 && T.lev_ptr[l] - T.lev_ptr[l - 1] == 1;
-    if (!chain) {
-      __syncthreads();
-      SPST(3 + nlev + (nlev - 1 - l));
-    }
+    SPST(2 + a.nlev);
+    sp_flow_back(a, T, S, X, F, w, lane, s_red[w], &s_bad);
+  } else {
+    sp_level_factor(a, T, w, lane, s_red[w], &s_bad);
+    sp_level_back<LT>(a, T, X, w, lane, s_red[w], &s_bad);
   }
   __syncthreads();
-  SPST(3 + 2 * nlev);
-  // the multi-workgroup factor launches (the wide steps) report through *a.bad
-  const int ext_bad = a.wide_steps > 0 ? *(volatile int*)a.bad : 0;
-  const bool failed = s_bad != 0 || ext_bad != 0;
-  ba_finish_step<8>(a, X, K, delta_thresh, failed, ((s_bad | ext_bad) & BA_BAD_STALL) != 0);
-  if (threadIdx.x == 0) *a.info = failed ? 1 : 0;
-  SPST(4 + 2 * nlev);
+  SPST(3 + 2 * a.nlev);
+  sp_finish(a, X, K, delta_thresh, s_bad);
+  SPST(4 + 2 * a.nlev);
 }
 
 }  // namespace m3s
@@ -599,19 +622,18 @@ static int ba_xcd_stride() {
   return xs;
 }
 
-// assembly (nL factor blocks + nb rhs rows), the wide steps, then the one-workgroup factor / solve / retraction.
-// step_tasks / step_base / step_na: per wide step its tasks, its first task record, its factor tasks (the rest are
-// update groups)
-extern "C" hipError_t m3s_launch_ba_solve(const BaArgs* a, int K, int nL, float delta_thresh, const int* step_tasks,
-                                          const int* step_base, const int* step_na, hipStream_t s) {
+// assembly (nL factor blocks + nb rhs rows), the wide steps (steps[l]: ba_pattern.h BaWideStep), then the one-workgroup
+// factor / solve / retraction
+extern "C" hipError_t m3s_launch_ba_solve(const BaArgs* a, int K, int nL, float delta_thresh, const BaWideStep* steps,
+                                          hipStream_t s) {
   const int xs = ba_xcd_stride();
   // the assembly stays spread over every XCD: pinned to XCD 0 (32 CUs, item-strided) it took longer than the L2 reads
   // it saved the first step (solve C5 0.381 vs 0.375 ms)
   if (a->nb > 0) hipLaunchKernelGGL(m3s::ba_assemble_kernel, dim3(nL + a->nb), dim3(64), 0, s, *a, nL);
   for (int l = 0; l < a->wide_steps; l++)
-    if (step_tasks[l] > 0)
-      hipLaunchKernelGGL(m3s::ba_sparse_step_kernel, dim3(step_tasks[l] * xs), dim3(64), 0, s, *a, step_base[l],
-                         step_na[l], xs);
+    if (steps[l].tasks > 0)
+      hipLaunchKernelGGL(m3s::ba_sparse_step_kernel, dim3(steps[l].tasks * xs), dim3(64), 0, s, *a, steps[l].base,
+                         steps[l].na, xs);
   // the tables, x and the flags in LDS when they fit (m3s_ba.h ba_sp_lds_bytes), else the global-table instance
   if (m3s::ba_sp_lds_bytes(a->plan_bytes, a->nb, a->flow != 0) <= (size_t)m3s::SP_PLAN_BYTES)
     hipLaunchKernelGGL(m3s::ba_sparse_factor_kernel<true>, dim3(1), dim3(1024), 0, s, *a, K, nL, delta_thresh);

@@ -5,24 +5,12 @@
 #include <stdint.h>
 #include <hip/hip_runtime.h>
 
+#include "ba_pattern.h"  // the plan's host-built half: BA_SYM_SECTIONS, BaStepRec, BaWideStep, M3S_BA_SP_WAVES, SP_PLAN_BYTES
+
 #define BA_MODE_POINTS 0
 #define BA_MODE_RAYS 1
 #define BA_MODE_CALIB 2
 #define BA_MODE_CALIB_RAW 3  // calib residuals on points NOT constrained to their pixel rays (m3s.h M3S_BA_MODE_CALIB_RAW)
-
-#ifndef M3S_BA_SP_WAVES
-#define M3S_BA_SP_WAVES 16  // waves of the one-workgroup sparse factorisation (ba_sparse.hip) and of its cost model (abi_ba.cpp)
-#endif
-namespace m3s {
-constexpr int SP_PLAN_BYTES = 144 * 1024;  // LDS of the one-workgroup factor kernel: the plan's loop tables and x
-// What that kernel keeps in LDS for a plan: the loop tables (plan_bytes: col_ptr .. sidx and, with flow, the dataflow
-// schedule; padded to 16 B), x (8 doubles per column) and, for the dataflow schedule, 3 flag words per column. A plan
-// that needs more than SP_PLAN_BYTES runs the global-table instance, level-synchronously: the host (build_symbolic)
-// drops its schedule by this rule and the launcher (m3s_launch_ba_solve) picks the instance by it.
-inline size_t ba_sp_lds_bytes(size_t plan_bytes, int nb, bool flow) {
-  return ((plan_bytes + 15) & ~(size_t)15) + (size_t)nb * 64 + (flow ? (size_t)nb * 12 : 0);
-}
-}  // namespace m3s
 
 struct BaParams {
   int mode;
@@ -81,8 +69,8 @@ struct BaArgs {
   const int* sidx;        // per group source, per block of column j: the source block of column k, or -1
   const int* sched;       // dataflow schedule of the one-workgroup part + back substitution (ba_pattern.h)
   int flow;               // sched present (else the level-synchronous loops)
-  const int4* step_rec;   // per task of the wide steps, 2 x int4: {j, b0, b1, pull group or -1}, {src begin, end, 0, 0}
-  const char* plan_lo;    // [plan_lo, plan_lo + plan_bytes): col_ptr .. sidx, sched, staged into LDS by the factor kernel
+  const BaStepRec* step_rec;  // per task of the wide steps (ba_pattern.h)
+  const char* plan_lo;    // [plan_lo, plan_lo + plan_bytes): the LDS-staged sections of BA_SYM_SECTIONS (ba_pattern.h)
   int plan_bytes;
   const int* asm_ptr;     // (nL+1) assembly CSR: edge*2 + (sign<0), edge order
   const int* asm_ent;
@@ -112,7 +100,7 @@ extern "C" {
 hipError_t m3s_launch_ba_kf_compare(const BaKfCopy* kf, int Kp, int N, uint8_t* dirty, hipStream_t s);
 hipError_t m3s_launch_ba_pack(const BaArgs* a, const BaParams* p, int n_pack, hipStream_t s);
 hipError_t m3s_launch_ba_lin(const BaArgs* a, const BaParams* p, int E_local, int pack, hipStream_t s);
-hipError_t m3s_launch_ba_solve(const BaArgs* a, int K, int nL, float delta_thresh, const int* step_tasks,
-                               const int* step_base, const int* step_na, hipStream_t s);
+hipError_t m3s_launch_ba_solve(const BaArgs* a, int K, int nL, float delta_thresh, const BaWideStep* steps,
+                               hipStream_t s);
 hipError_t m3s_launch_ba_solve_dense(const BaArgs* a, int K, int nL, float delta_thresh, hipStream_t s);  // ba_dense.hip
 }

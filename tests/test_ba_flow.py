@@ -1,6 +1,8 @@
 """Host check of the BA dataflow schedule (csrc/ba_pattern.cpp ba_flow_schedule): scripts/ba_flow_check.cpp
 interprets every wave's task list with ba_sparse_factor_kernel's wait conditions and fails on a deadlock, an
-update group applied out of step order, a column factored before its groups landed, or an unfinished column."""
+update group applied out of step order, a column factored before its groups landed, or an unfinished column. For
+every graph it also builds the plan (ba_build_plan) under four option sets and checks each packed image against its
+source vectors and each wide-step task record against the tables."""
 import os
 import shutil
 import subprocess
@@ -17,8 +19,14 @@ def checker(tmp_path_factory):
     if cxx is None:
         pytest.skip("no host C++ compiler")
     exe = str(tmp_path_factory.mktemp("flow") / "ba_flow_check")
-    subprocess.check_call([cxx, "-O2", "-std=c++17", "-I", CSRC, os.path.join(REPO, "scripts", "ba_flow_check.cpp"),
-                           os.path.join(CSRC, "ba_pattern.cpp"), "-o", exe])
+    build = [cxx, "-O2", "-std=c++17", "-I", CSRC, os.path.join(REPO, "scripts", "ba_flow_check.cpp"),
+             os.path.join(CSRC, "ba_pattern.cpp"), "-o", exe]
+    # a stand-alone host program: under AddressSanitizer and UBSan (any report ends the run with a failure) where
+    # the compiler links their runtimes, statically so the program does not depend on how it is loaded; else plain
+    san = ["-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-static-libasan",
+           "-static-libubsan"]
+    if subprocess.run(build + san, capture_output=True).returncode != 0:
+        subprocess.check_call(build)
     return exe
 
 
