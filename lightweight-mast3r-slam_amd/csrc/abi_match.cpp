@@ -51,8 +51,6 @@ struct MatchWs {
   float* rays9;   // (B,H,W,9) rays + gradients
   void* D11h;     // f16: (B,3,H,W,8) chunk planes on the refine tile path, else (B,H,W,F)
   int* p1;        // (B,N,2) int32
-  int4* olist;    // (B*N) refine deferred-outlier records
-  int* ocount;    // refine deferred-outlier count
   float* cpart;   // the refine screen's norm bound, prep's tile partials (m3s_prep_parts)
   float* cmax;    // ... reduced by the proj launch (refine.hip SCREEN)
 };
@@ -62,8 +60,6 @@ static size_t match_carve(Carver& c, int B, int H, int W, int F, MatchWs* w) {
   w->rays9 = c.take<float>((size_t)B * H * W * 9);
   w->D11h = c.take<uint16_t>((size_t)B * H * W * F);
   w->p1 = c.take<int>((size_t)B * H * W * 2);
-  w->olist = c.take<int4>((size_t)B * H * W);
-  w->ocount = c.take<int>(1);
   w->cpart = c.take<float>((size_t)m3s_prep_parts(B, H, W));
   w->cmax = c.take<float>(1);
   return c.off;
@@ -100,17 +96,10 @@ extern "C" int m3s_match(const float* X11, const float* X21, const float* D11, c
                             screen ? w.cpart : nullptr, s),
             "match prep launch");
   }
-  // every wave scores its window outliers in place (no deferred list, no refine_outlier_kernel launch: on coherent
-  // inputs the list is empty and the launch alone cost ~2 us per frame; a scattered warm start, every lane an
-  // outlier, costs its waves 64 pixels x 5 levels serially). M3S_REFINE_INPLACE=0: waves with more than
-  // RT_INPLACE_MAX outliers defer them to the list and the outlier launch
-  const bool inplace = env_flag("M3S_REFINE_INPLACE", true);
   // the tile path runs the projection search inside the refine launch (refine.hip FUSE_PROJ: two launches per match,
   // no p1 round trip; same idx / valid bit for bit). M3S_MATCH_FUSE_PROJ=0 (read per call so tests can compare both)
-  // restores the proj_occlusion launch, and so does the deferred list (M3S_REFINE_INPLACE=0): its counter is
-  // cleared by that launch
-  const bool fuse = planar && inplace && env_flag("M3S_MATCH_FUSE_PROJ", true) &&
-                    (size_t)9 * H * W < ((size_t)1 << 31);
+  // restores the proj_occlusion launch
+  const bool fuse = planar && env_flag("M3S_MATCH_FUSE_PROJ", true) && (size_t)9 * H * W < ((size_t)1 << 31);
   if (fuse) {
     Span sp("refine_lin", s);
     HIP_TRY(m3s_launch_refine_tile_proj(w.D11h, D21, idx_out, valid_out, w.rays9, X11, X21, idx_init, B, H, W, F, radius,
@@ -122,7 +111,7 @@ extern "C" int m3s_match(const float* X11, const float* X21, const float* D11, c
   {
     Span sp("proj_occlusion", s);
     HIP_TRY(m3s_launch_proj_occlusion(w.rays9, X11, X21, idx_init, w.p1, valid_out, B, H, W, max_iter, lambda_init,
-                                      cost_thresh, dist_thresh, w.ocount, w.cpart, m3s_prep_parts(B, H, W),
+                                      cost_thresh, dist_thresh, w.cpart, m3s_prep_parts(B, H, W),
                                       screen ? w.cmax : nullptr, s),
             "match proj launch");
   }
@@ -131,8 +120,7 @@ extern "C" int m3s_match(const float* X11, const float* X21, const float* D11, c
   {
     Span sp("refine_lin", s);
     HIP_TRY(m3s_launch_refine_lin(w.D11h, D21, w.p1, idx_out, B, H, W, F, radius, radius > 0 ? dilation_max : 0,
-                                  inplace ? nullptr : w.olist,
-                                  w.ocount, screen ? w.cmax : nullptr, s),
+                                  screen ? w.cmax : nullptr, s),
             "match refine launch");
   }
   return M3S_OK;

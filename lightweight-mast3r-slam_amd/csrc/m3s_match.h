@@ -14,20 +14,18 @@ hipError_t m3s_launch_iter_proj(const float* rays, const float* pts, const float
                                 hipStream_t s);
 hipError_t m3s_launch_proj_occlusion(const float* rays, const float* X11, const float* X21, const int64_t* idx_init,
                                      int* p1, uint8_t* valid, int B, int H, int W, int max_iter, float lambda_init,
-                                     float cost_thresh, float dist_thresh, int* zero_counter, const float* cnorm_part,
-                                     int nparts, float* cmax, hipStream_t s);
+                                     float cost_thresh, float dist_thresh, const float* cnorm_part, int nparts,
+                                     float* cmax, hipStream_t s);
 hipError_t m3s_launch_refine_f16(const void* D11, const void* D21, const int64_t* p1, int64_t* p1_new, int B, int H,
                                  int W, int F, int N, int radius, int dilation_max, hipStream_t s);
 hipError_t m3s_launch_refine_f32(const float* D11, const float* D21, const int64_t* p1, int64_t* p1_new, int B, int H,
                                  int W, int F, int N, int radius, int dilation_max, hipStream_t s);
 hipError_t m3s_launch_refine_lin(const void* D11h, const float* D21, const int* p1, int64_t* idx_out, int B, int H,
-                                 int W, int F, int radius, int dilation_max, void* olist, int* ocount,
-                                 const float* cmax, hipStream_t s);
+                                 int W, int F, int radius, int dilation_max, const float* cmax, hipStream_t s);
 // ---- refine.hip ----
 int m3s_refine_tile_ok(int B, int H, int W, int F, int radius, int dilation_max);
 hipError_t m3s_launch_refine_tile(const void* D11h, const void* D21, const void* p1, void* out, int B, int H, int W,
-                                  int F, int radius, int dilation_max, int fused, void* olist, int* ocount,
-                                  const float* cmax, hipStream_t s);
+                                  int F, int radius, int dilation_max, int fused, const float* cmax, hipStream_t s);
 hipError_t m3s_launch_refine_tile_proj(const void* D11h, const float* D21, int64_t* idx_out, uint8_t* valid,
                                        const float* rays9, const float* X11, const float* X21, const int64_t* idx_init,
                                        int B, int H, int W, int F, int radius, int dilation_max, int max_iter,

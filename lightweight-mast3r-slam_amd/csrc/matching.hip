@@ -57,7 +57,7 @@ __device__ __forceinline__ float desc_planar(const float4 v[6], h1* __restrict__
 template <int DMODE>
 __global__ void __launch_bounds__(256) prep_rays_kernel(const float* __restrict__ X11, float* __restrict__ rays9,
                                                         const float* __restrict__ D11, h1* __restrict__ D11h, int H,
-                                                        int W, int F, int planar, float* __restrict__ cnorm_part) {
+                                                        int W, int F, float* __restrict__ cnorm_part) {
   __shared__ float tile[(PREP_T + 2) * (PREP_T + 2) * 3];
   const int b = blockIdx.z;
   const int u0 = blockIdx.x * PREP_T, v0 = blockIdx.y * PREP_T;
@@ -191,14 +191,13 @@ __global__ void __launch_bounds__(256) iter_proj_kernel(const float* __restrict_
 __global__ void __launch_bounds__(256) proj_occlusion_kernel(
     const float* __restrict__ rays, const float* __restrict__ X11, const float* __restrict__ X21,
     const int64_t* __restrict__ idx_init, int* __restrict__ p1, uint8_t* __restrict__ valid, int H, int W,
-    int max_iter, float lambda_init, float cost_thresh, float dist_thresh, int* zero_counter,
-    const float* __restrict__ cnorm_part, int nparts, float* __restrict__ cmax) {
+    int max_iter, float lambda_init, float cost_thresh, float dist_thresh, const float* __restrict__ cnorm_part,
+    int nparts, float* __restrict__ cmax) {
   const int N = H * W;
   if (cmax != nullptr && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x < 64) reduce_cnorm(cnorm_part, nparts, cmax);
   // contiguous pixel runs per XCD: each XCD's L2 then holds the rays rows its LM gathers touch
   const int n = xcd_remap(blockIdx.x, gridDim.x) * blockDim.x + threadIdx.x;
   const int b = blockIdx.y;
-  if (zero_counter != nullptr && n == 0 && b == 0) *zero_counter = 0;  // refine's outlier list (next launch)
   if (n >= N) return;
   const size_t bn = (size_t)b * N + n;
   const float x = X21[bn * 3 + 0], y = X21[bn * 3 + 1], z = X21[bn * 3 + 2];
@@ -244,10 +243,12 @@ __device__ __forceinline__ h1 score_f16(const h2* q, const h1* __restrict__ c) {
   return s;
 }
 
-template <int F>
-__device__ __forceinline__ void refine_point(const h1* __restrict__ img, int H, int W, const h2* q, int radius,
-                                             int dilation_max, int& u0, int& v0) {
-  h1 max_score = (h1)0.0f;  // cuda::std::numeric_limits<c10::Half>::min() == Half() == +0
+// The levels of one query: score(pix) is candidate pixel pix's score, start the running max's first value, the
+// reference's numeric_limits<scalar_t>::min()
+template <class S, class Score>
+__device__ __forceinline__ void refine_point(int H, int W, int radius, int dilation_max, S start, int& u0, int& v0,
+                                             Score score) {
+  S max_score = start;
   int u_new = u0, v_new = v0;
   for (int d = dilation_max; d > 0; d--) {
     const int rd = radius * d;
@@ -257,7 +258,7 @@ __device__ __forceinline__ void refine_point(const h1* __restrict__ img, int H, 
       for (int j = 0; j < diam; j += d) {
         const int v = v0 - rd + j;
         if (v >= 0 && v < H && u >= 0 && u < W) {
-          const h1 s = score_f16<F>(q, img + ((size_t)v * W + u) * F);
+          const S s = score((size_t)v * W + u);
           if (s > max_score) {
             max_score = s;
             u_new = u;
@@ -269,6 +270,13 @@ __device__ __forceinline__ void refine_point(const h1* __restrict__ img, int H, 
     u0 = u_new;
     v0 = v_new;
   }
+}
+// ... with the c10::Half score; the start value is numeric_limits<c10::Half>::min() == Half() == +0
+template <int F>
+__device__ __forceinline__ void refine_point_f16(const h1* __restrict__ img, int H, int W, const h2* q, int radius,
+                                                 int dilation_max, int& u0, int& v0) {
+  refine_point(H, W, radius, dilation_max, (h1)0.0f, u0, v0,
+               [&](size_t pix) { return score_f16<F>(q, img + pix * F); });
 }
 
 // Reference signature: D11 (B,H,W,F) f16, D21 (B,N,F) f16, p1 (B,N,2) i64 -> p1_new (B,N,2) i64.
@@ -283,7 +291,7 @@ __global__ void __launch_bounds__(256) refine_f16_kernel(const h1* __restrict__ 
   h2 q[F / 2];
   load_query<F, false>(D21, bn, q);
   int u0 = (int)p1[bn * 2 + 0], v0 = (int)p1[bn * 2 + 1];
-  refine_point<F>(D11 + (size_t)b * H * W * F, H, W, q, radius, dilation_max, u0, v0);
+  refine_point_f16<F>(D11 + (size_t)b * H * W * F, H, W, q, radius, dilation_max, u0, v0);
   p1_new[bn * 2 + 0] = u0;
   p1_new[bn * 2 + 1] = v0;
 }
@@ -301,7 +309,7 @@ __global__ void __launch_bounds__(256) refine_lin_kernel(const h1* __restrict__ 
   h2 q[F / 2];
   load_query<F, true>(D21, bn, q);
   int u0 = p1[bn * 2 + 0], v0 = p1[bn * 2 + 1];
-  refine_point<F>(D11h + (size_t)b * H * W * F, H, W, q, radius, dilation_max, u0, v0);
+  refine_point_f16<F>(D11h + (size_t)b * H * W * F, H, W, q, radius, dilation_max, u0, v0);
   idx_out[bn] = (int64_t)u0 + (int64_t)W * v0;
 }
 
@@ -316,28 +324,12 @@ __global__ void __launch_bounds__(256) refine_f32_kernel(const float* __restrict
   const float* q = D21 + bn * F;
   const float* img = D11 + (size_t)b * H * W * F;
   int u0 = (int)p1[bn * 2 + 0], v0 = (int)p1[bn * 2 + 1];
-  float max_score = 1.17549435e-38f;  // FLT_MIN
-  int u_new = u0, v_new = v0;
-  for (int d = dilation_max; d > 0; d--) {
-    const int rd = radius * d, diam = 2 * rd + 1;
-    for (int i = 0; i < diam; i += d) {
-      for (int j = 0; j < diam; j += d) {
-        const int u = u0 - rd + i, v = v0 - rd + j;
-        if (v >= 0 && v < H && u >= 0 && u < W) {
-          const float* c = img + ((size_t)v * W + u) * F;
-          float s = 0.0f;
-          for (int k = 0; k < F; k++) s += q[k] * c[k];
-          if (s > max_score) {
-            max_score = s;
-            u_new = u;
-            v_new = v;
-          }
-        }
-      }
-    }
-    u0 = u_new;
-    v0 = v_new;
-  }
+  refine_point(H, W, radius, dilation_max, 1.17549435e-38f /* FLT_MIN */, u0, v0, [&](size_t pix) {
+    const float* c = img + pix * F;
+    float s = 0.0f;
+    for (int k = 0; k < F; k++) s += q[k] * c[k];
+    return s;
+  });
   p1_new[bn * 2 + 0] = u0;
   p1_new[bn * 2 + 1] = v0;
 }
@@ -353,7 +345,7 @@ extern "C" hipError_t m3s_launch_prep(const float* X11, float* rays9, const floa
                                       int W, int F, int planar, float* cnorm_part, hipStream_t s) {
   dim3 grid((W + PREP_T - 1) / PREP_T, (H + PREP_T - 1) / PREP_T, B);
   auto k = D11 == nullptr ? m3s::prep_rays_kernel<0> : planar ? m3s::prep_rays_kernel<1> : m3s::prep_rays_kernel<2>;
-  hipLaunchKernelGGL(k, grid, dim3(256), 0, s, X11, rays9, D11, reinterpret_cast<m3s::h1*>(D11h), H, W, F, planar,
+  hipLaunchKernelGGL(k, grid, dim3(256), 0, s, X11, rays9, D11, reinterpret_cast<m3s::h1*>(D11h), H, W, F,
                      cnorm_part);
   return hipGetLastError();
 }
@@ -375,13 +367,24 @@ extern "C" hipError_t m3s_launch_iter_proj(const float* rays, const float* pts, 
 extern "C" hipError_t m3s_launch_proj_occlusion(const float* rays, const float* X11, const float* X21,
                                                 const int64_t* idx_init, int* p1, uint8_t* valid, int B, int H, int W,
                                                 int max_iter, float lambda_init, float cost_thresh, float dist_thresh,
-                                                int* zero_counter, const float* cnorm_part, int nparts, float* cmax,
-                                                hipStream_t s) {
+                                                const float* cnorm_part, int nparts, float* cmax, hipStream_t s) {
   if ((size_t)9 * H * W >= ((size_t)1 << 31)) return hipErrorInvalidValue;  // bilin_sample9's 32-bit offsets
   // cmax (nullable): one wave reduces prep's tile partials into the refine screen's bound
   dim3 grid((H * W + 255) / 256, B);
   hipLaunchKernelGGL(m3s::proj_occlusion_kernel, grid, dim3(256), 0, s, rays, X11, X21, idx_init, p1, valid, H, W,
-                     max_iter, lambda_init, cost_thresh, dist_thresh, zero_counter, cnorm_part, nparts, cmax);
+                     max_iter, lambda_init, cost_thresh, dist_thresh, cnorm_part, nparts, cmax);
+  return hipGetLastError();
+}
+
+// the one place the per-pixel refine kernels' F becomes a template argument: launch(std::integral_constant<int, F>{})
+template <class L>
+static hipError_t refine_with_F(int F, L&& launch) {
+  switch (F) {
+    case 16: launch(std::integral_constant<int, 16>{}); break;
+    case 24: launch(std::integral_constant<int, 24>{}); break;
+    case 32: launch(std::integral_constant<int, 32>{}); break;
+    default: return hipErrorInvalidValue;
+  }
   return hipGetLastError();
 }
 
@@ -391,26 +394,12 @@ extern "C" hipError_t m3s_launch_refine_f16(const void* D11, const void* D21, co
   const m3s::h1* a = reinterpret_cast<const m3s::h1*>(D11);
   const m3s::h1* q = reinterpret_cast<const m3s::h1*>(D21);
   if (N == H * W &&
-      m3s_launch_refine_tile(D11, D21, p1, p1_new, B, H, W, F, radius, dilation_max, 0, nullptr, nullptr, nullptr, s) ==
-          hipSuccess)
+      m3s_launch_refine_tile(D11, D21, p1, p1_new, B, H, W, F, radius, dilation_max, 0, nullptr, s) == hipSuccess)
     return hipSuccess;  // tiled LDS path (query n is pixel n of the grid)
-  switch (F) {
-    case 24:
-      hipLaunchKernelGGL(m3s::refine_f16_kernel<24>, grid, dim3(256), 0, s, a, q, p1, p1_new, H, W, N, radius,
-                         dilation_max);
-      break;
-    case 16:
-      hipLaunchKernelGGL(m3s::refine_f16_kernel<16>, grid, dim3(256), 0, s, a, q, p1, p1_new, H, W, N, radius,
-                         dilation_max);
-      break;
-    case 32:
-      hipLaunchKernelGGL(m3s::refine_f16_kernel<32>, grid, dim3(256), 0, s, a, q, p1, p1_new, H, W, N, radius,
-                         dilation_max);
-      break;
-    default:
-      return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
+  return refine_with_F(F, [&](auto f) {
+    hipLaunchKernelGGL(m3s::refine_f16_kernel<decltype(f)::value>, grid, dim3(256), 0, s, a, q, p1, p1_new, H, W, N,
+                       radius, dilation_max);
+  });
 }
 
 extern "C" hipError_t m3s_launch_refine_f32(const float* D11, const float* D21, const int64_t* p1, int64_t* p1_new,
@@ -422,30 +411,16 @@ extern "C" hipError_t m3s_launch_refine_f32(const float* D11, const float* D21, 
   return hipGetLastError();
 }
 
-// olist/ocount: deferred-outlier list (B*H*W int4) + counter, zeroed by proj_occlusion_kernel
 extern "C" hipError_t m3s_launch_refine_lin(const void* D11h, const float* D21, const int* p1, int64_t* idx_out, int B,
-                                            int H, int W, int F, int radius, int dilation_max, void* olist,
-                                            int* ocount, const float* cmax, hipStream_t s) {
+                                            int H, int W, int F, int radius, int dilation_max, const float* cmax,
+                                            hipStream_t s) {
   dim3 grid((H * W + 255) / 256, B);
   const m3s::h1* a = reinterpret_cast<const m3s::h1*>(D11h);
   // tiled LDS path exactly when m3s_refine_tile_ok (prep wrote the PLANAR D11h then)
   if (radius > 0 && m3s_refine_tile_ok(B, H, W, F, radius, dilation_max))
-    return m3s_launch_refine_tile(D11h, D21, p1, idx_out, B, H, W, F, radius, dilation_max, 1, olist, ocount, cmax, s);
-  switch (F) {
-    case 24:
-      hipLaunchKernelGGL(m3s::refine_lin_kernel<24>, grid, dim3(256), 0, s, a, D21, p1, idx_out, H, W, radius,
-                         dilation_max);
-      break;
-    case 16:
-      hipLaunchKernelGGL(m3s::refine_lin_kernel<16>, grid, dim3(256), 0, s, a, D21, p1, idx_out, H, W, radius,
-                         dilation_max);
-      break;
-    case 32:
-      hipLaunchKernelGGL(m3s::refine_lin_kernel<32>, grid, dim3(256), 0, s, a, D21, p1, idx_out, H, W, radius,
-                         dilation_max);
-      break;
-    default:
-      return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
+    return m3s_launch_refine_tile(D11h, D21, p1, idx_out, B, H, W, F, radius, dilation_max, 1, cmax, s);
+  return refine_with_F(F, [&](auto f) {
+    hipLaunchKernelGGL(m3s::refine_lin_kernel<decltype(f)::value>, grid, dim3(256), 0, s, a, D21, p1, idx_out, H, W,
+                       radius, dilation_max);
+  });
 }

@@ -18,13 +18,10 @@
 //   * Levels are specialised on d, so every candidate read is one ds_read_b128 with an immediate
 //     offset from a single per-lane base; the 49 running half sums live in registers across the
 //     three chunks (the sum stays sequential over k = 0..23: c10::Half step rounding unchanged).
-//   * A lane whose 49 candidates do not fit the window (an outlier centre, a clipped window) is
-//     DEFERRED: its state (pixel, centre, running max, level) is appended to a list and the lane
-//     leaves the tile (it no longer widens the window of later levels). refine_outlier_kernel then
-//     finishes every deferred pixel with one wave per pixel: 49 lanes score the 49 candidates from
-//     global memory (all loads in flight at once) and a first-maximum wave arg-max reproduces the
-//     sequential strict-'>' scan (the running max only grows from +0). Without a list (reference
-//     op path, no workspace) the wave scores its outliers in place, one at a time (wave_level).
+//   * A lane whose 49 candidates do not fit the window (an outlier centre, a clipped window) is a
+//     window outlier: its wave scores it in place, one outlier at a time (wave_level): 49 lanes
+//     score the 49 candidates from global memory (all loads in flight at once) and a first-maximum
+//     wave arg-max reproduces the sequential strict-'>' scan (the running max only grows from +0).
 //   * Tiles are dealt to XCDs in contiguous runs (bijective remap) so each XCD's 4 MiB L2 holds
 //     its slab of D11.
 //   * On the fused match path the same launch first runs the projection search for the tile's pixels (FUSE_PROJ,
@@ -54,7 +51,6 @@ constexpr int RT_DROWS = 26, RT_DBUF = RT_DROWS * RT_PCOLS;
 static_assert(RT_TH == 2 * RT_WAVES, "two pixel rows per wave");
 static_assert(3 * RT_PROWS * RT_PCOLS <= RT_ROWS * RT_COLS && 2 * RT_DROWS * RT_PCOLS <= RT_ROWS * RT_COLS,
               "the packed and double-buffered windows share the block's window");
-constexpr int RT_INPLACE_MAX = 8;  // window outliers a wave scores in place at one level (more: deferred to the list)
 
 typedef __attribute__((address_space(1))) const void* gvoid_t;
 typedef __attribute__((address_space(3))) void* lvoid_t;
@@ -92,8 +88,8 @@ __device__ __forceinline__ void rt_prio_from() {
 }
 
 // Measurement builds. Each is a pair of helpers that compile to nothing without its macro.
-// M3S_REFINE_STATS (the counts quoted in DESIGN section 4; m3s_debug_refine_stats reads them): per level d, deferred
-// lanes [2d] and waves [2d + 1]; survivors, the lanes' sum [32 + 2d] and the per-wave maximum summed [33 + 2d].
+// M3S_REFINE_STATS (the counts quoted in DESIGN section 4; m3s_debug_refine_stats reads them): per level d, window
+// outlier lanes [2d] and waves [2d + 1]; survivors, the lanes' sum [32 + 2d] and the per-wave maximum summed [33 + 2d].
 #ifdef M3S_REFINE_STATS
 __device__ unsigned long long g_refine_stats[64];
 #endif
@@ -364,9 +360,6 @@ struct TileCtx {
   int H, W, lane, wid, u_pix, v_pix;
   int fu, fv;   // tile flow estimate: mean initial centre displacement (fixed for all levels)
   int tcu, tcv; // tile centre + flow estimate: the window's centre when the centres' cover does not fit
-  int bn;       // batch * N + pixel
-  int4* olist;  // deferred-pixel list (nullable: score outliers in place)
-  int* ocount;
   float bq = 0.0f;   // SCREEN: this lane's bound B (0.0125 |q| cmax + 2^-18)
   bool sok = false;  // SCREEN: the bound is usable (|q| cmax <= 16384 and finite)
 };
@@ -450,7 +443,7 @@ __device__ __forceinline__ LevelWin level_window(const TileCtx& t, bool active, 
   }
   // window placement: exact bbox cover when it fits, else centred on the tile's centre displaced by its flow
   // estimate. A cover that does not fit is mostly a tight cluster plus a few far centres at one end: centring on the
-  // bbox middle deferred the cluster itself (d = 4 on the synthetic 512x512 pair: 1502 deferred lanes against 54,
+  // bbox middle left the cluster itself outside (d = 4 on the synthetic 512x512 pair: 1502 outlier lanes against 54,
   // scripts/refine_window_stats.py)
   const int x_lo = mnu - RD, x_hi = mxu + RD, y_lo = mnv - RD, y_hi = mxv + RD;
   LevelWin w;
@@ -470,54 +463,34 @@ __device__ __forceinline__ LevelWin level_window(const TileCtx& t, bool active, 
   return w;
 }
 
-// The wave's window outliers (outl: active lanes whose 49 candidates do not fit the window): deferred to the list, or
-// scored in place
+// The wave's window outliers (outl: active lanes whose 49 candidates do not fit the window), scored in place: the
+// wave takes them one at a time, one wave-level each, while the rest of the tile waits at the next barrier (a
+// scattered warm start, every lane an outlier, costs its waves 64 pixels per level serially)
 template <int D, bool PLANAR>
-__device__ __forceinline__ void level_outliers(const TileCtx& t, bool outl, bool& active, const h2* q, int& cu,
-                                               int& cv, h1& max_score) {
+__device__ __forceinline__ void level_outliers(const TileCtx& t, bool outl, const h2* q, int& cu, int& cv,
+                                               h1& max_score) {
   constexpr int F = 24;
   const int lane = t.lane;
-  const uint64_t om = __ballot(outl);
-  stats_outliers<D>(lane, om);
-  if (om) {
-    // a wave with a few window outliers scores them in place (one wave-level each, while the rest of the tile waits
-    // at the next barrier); more than RT_INPLACE_MAX go to the deferred list (one wave per pixel in
-    // refine_outlier_kernel), which keeps pathological inputs (scattered warm starts: every lane an outlier) parallel
-    if (t.olist != nullptr && __popcll(om) > RT_INPLACE_MAX) {
-      // defer: one atomic per wave reserves the slots, lanes write {pixel, centre, max bits, level}
-      const int leader = __ffsll((long long)om) - 1;
-      int base = 0;
-      if (lane == leader) base = atomicAdd(t.ocount, __popcll(om));
-      base = __shfl(base, leader, 64);
-      if (outl) {
-        const int rank = __popcll(om & ((1ull << lane) - 1ull));
-        const unsigned short mb = *reinterpret_cast<const unsigned short*>(&max_score);
-        t.olist[base + rank] = make_int4(t.bn, (cu & 0xffff) | (cv << 16), (int)mb | (D << 16), 0);
-        active = false;
-      }
-    } else {
-      // in place: the wave takes its outliers one at a time
-      uint64_t m = om;
-      while (m) {
-        const int src = __ffsll((long long)m) - 1;
-        m &= m - 1;
-        int scu = __shfl(cu, src, 64), scv = __shfl(cv, src, 64);
-        const unsigned short mb0 = (unsigned short)__shfl((int)*reinterpret_cast<const unsigned short*>(&max_score),
-                                                          src, 64);
-        h1 smax = *reinterpret_cast<const h1*>(&mb0);
-        h2 sq[F / 2];
+  uint64_t m = __ballot(outl);
+  stats_outliers<D>(lane, m);
+  while (m) {
+    const int src = __ffsll((long long)m) - 1;
+    m &= m - 1;
+    int scu = __shfl(cu, src, 64), scv = __shfl(cv, src, 64);
+    const unsigned short mb0 = (unsigned short)__shfl((int)*reinterpret_cast<const unsigned short*>(&max_score),
+                                                      src, 64);
+    h1 smax = *reinterpret_cast<const h1*>(&mb0);
+    h2 sq[F / 2];
 #pragma unroll
-        for (int k = 0; k < F / 2; k++) {
-          const int v = __shfl(*reinterpret_cast<const int*>(&q[k]), src, 64);
-          sq[k] = *reinterpret_cast<const h2*>(&v);
-        }
-        wave_level<D, PLANAR>(t.img, t.H, t.W, sq, scu, scv, smax, lane);
-        if (lane == src) {
-          cu = scu;
-          cv = scv;
-          max_score = smax;
-        }
-      }
+    for (int k = 0; k < F / 2; k++) {
+      const int v = __shfl(*reinterpret_cast<const int*>(&q[k]), src, 64);
+      sq[k] = *reinterpret_cast<const h2*>(&v);
+    }
+    wave_level<D, PLANAR>(t.img, t.H, t.W, sq, scu, scv, smax, lane);
+    if (lane == src) {
+      cu = scu;
+      cv = scv;
+      max_score = smax;
     }
   }
 }
@@ -682,7 +655,7 @@ __device__ __forceinline__ void exact_level(const TileCtx& t, const LevelWin& w,
 
 // One level of the tile: window, outliers, then the screened or the exact scoring of the lanes in the window
 template <int D, bool SCREEN, bool PLANAR>
-__device__ __forceinline__ void refine_level(const TileCtx& t, bool& active, const h2* q, int& cu, int& cv,
+__device__ __forceinline__ void refine_level(const TileCtx& t, bool active, const h2* q, int& cu, int& cv,
                                              h1& max_score, uint4* lds, int (*s_red)[4], bool first) {
   constexpr int RD = 3 * D;
   rt_prio<RT_PRIO_START, D>();  // three other waves wait at the exchange's barriers
@@ -693,7 +666,7 @@ __device__ __forceinline__ void refine_level(const TileCtx& t, bool& active, con
   g.bx = g.u_lo - w.wx0;
   g.by = g.v_lo - w.wy0;
   g.in = active && g.bx >= 0 && g.bx + 2 * RD < w.ncols && g.by >= 0 && g.by + 2 * RD < w.nrows;
-  level_outliers<D, PLANAR>(t, active && !g.in, active, q, cu, cv, max_score);
+  level_outliers<D, PLANAR>(t, active && !g.in, q, cu, cv, max_score);
   if constexpr (SCREEN)
     screened_level<D, PLANAR>(t, w, g, q, cu, cv, max_score, lds, first);
   else
@@ -831,12 +804,12 @@ __device__ __forceinline__ void screen_bound(TileCtx& t, const h2* q, float cm) 
 // shared m3s_proj.hpp, so the centres and valid are bit-identical): each lane projects its own pixel, keeps the
 // centre in registers (no p1 traffic), writes valid and goes on into the levels; one wave per block reduces prep's
 // norm partials itself (no launch sits between prep and this one; the max is order-independent, so every block gets
-// the same bits). Runs without a deferred list only (olist == nullptr: nothing clears ocount in front of it).
+// the same bits).
 template <bool D21_F32, bool P1_I64, bool LIN_OUT, bool SCREEN, bool FUSE_PROJ = false>
 __global__ void __launch_bounds__(RT_THREADS, RT_MIN_BLOCKS)
     refine_tile_kernel(const h1* __restrict__ D11h, const void* __restrict__ D21, const void* __restrict__ p1v,
                        void* __restrict__ outv, int H, int W, int dilation_max, int tiles_x, int tiles_per_img,
-                       int nblocks, int4* olist, int* ocount, const float* __restrict__ cmaxp, const ProjArgs pa) {
+                       int nblocks, const float* __restrict__ cmaxp, const ProjArgs pa) {
   constexpr int F = 24;
   static_assert(!FUSE_PROJ || (D21_F32 && !P1_I64 && LIN_OUT), "the fused projection feeds the fused match path");
   const unsigned long long stamp_top = bstamp_clock();
@@ -859,12 +832,9 @@ __global__ void __launch_bounds__(RT_THREADS, RT_MIN_BLOCKS)
     t.u_pix = tx * RT_TW + g * 16 + r;
     t.v_pix = ty * RT_TH + 2 * t.wid + (t.lane >> 5);
   }
-  t.olist = olist;
-  t.ocount = ocount;
-  bool active = t.u_pix < W && t.v_pix < H;
+  const bool active = t.u_pix < W && t.v_pix < H;
   const int N = H * W;
   const size_t bn = (size_t)b * N + (size_t)t.v_pix * W + t.u_pix;
-  t.bn = (int)bn;
   t.img = D11h + (size_t)b * N * F;
   h2 q[F / 2];
   int cu = 0, cv = 0;
@@ -892,7 +862,6 @@ __global__ void __launch_bounds__(RT_THREADS, RT_MIN_BLOCKS)
     }
   }
   if constexpr (SCREEN) screen_bound(t, q, FUSE_PROJ ? cmax_b : *cmaxp);
-  const bool mine = active;  // deferred pixels are written by refine_outlier_kernel
   bstamp_levels_start(FUSE_PROJ, stamp_top);
   h1 max_score = (h1)0.0f;   // numeric_limits<c10::Half>::min() == +0, never reset between levels
   // the levels as straight-line code (d = dilation_max .. 1) instead of a loop over a switch of the eight inlined level
@@ -912,57 +881,17 @@ __global__ void __launch_bounds__(RT_THREADS, RT_MIN_BLOCKS)
   RT_LEVEL(1)
 #undef RT_LEVEL
   rt_prio<0>();
-  if (mine && active) store_out<LIN_OUT>(outv, bn, W, cu, cv);
+  if (active) store_out<LIN_OUT>(outv, bn, W, cu, cv);
   bstamp_block_end(FUSE_PROJ, stamp_lm, active, lds);
-}
-
-// Finishes the deferred pixels: one wave per pixel, levels d0..1 by wave_level (grid-stride over
-// the list; the count is read on the device, so the launch needs no host sync).
-template <bool D21_F32, bool LIN_OUT>
-__global__ void __launch_bounds__(256) refine_outlier_kernel(const h1* __restrict__ D11h,
-                                                             const void* __restrict__ D21, void* __restrict__ outv,
-                                                             int H, int W, const int4* __restrict__ olist,
-                                                             const int* __restrict__ ocount) {
-  constexpr int F = 24;
-  const int lane = threadIdx.x & 63;
-  const int nwaves = gridDim.x * (blockDim.x >> 6);
-  const int count = *ocount;
-  const int N = H * W;
-  for (int o = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); o < count; o += nwaves) {
-    const int4 r = olist[o];
-    const size_t bn = (size_t)r.x;
-    int cu = (int)(short)(r.y & 0xffff), cv = r.y >> 16;
-    const unsigned short mb = (unsigned short)(r.z & 0xffff);
-    h1 max_score = *reinterpret_cast<const h1*>(&mb);
-    const int d0 = r.z >> 16;
-    const h1* img = D11h + (bn / N) * (size_t)N * F;
-    h2 q[F / 2];
-    load_query<F, D21_F32>(D21, bn, q);
-    for (int d = d0; d > 0; d--) {
-      switch (d) {
-        case 8: wave_level<8, LIN_OUT>(img, H, W, q, cu, cv, max_score, lane); break;
-        case 7: wave_level<7, LIN_OUT>(img, H, W, q, cu, cv, max_score, lane); break;
-        case 6: wave_level<6, LIN_OUT>(img, H, W, q, cu, cv, max_score, lane); break;
-        case 5: wave_level<5, LIN_OUT>(img, H, W, q, cu, cv, max_score, lane); break;
-        case 4: wave_level<4, LIN_OUT>(img, H, W, q, cu, cv, max_score, lane); break;
-        case 3: wave_level<3, LIN_OUT>(img, H, W, q, cu, cv, max_score, lane); break;
-        case 2: wave_level<2, LIN_OUT>(img, H, W, q, cu, cv, max_score, lane); break;
-        default: wave_level<1, LIN_OUT>(img, H, W, q, cu, cv, max_score, lane); break;
-      }
-    }
-    if (lane == 0) store_out<LIN_OUT>(outv, bn, W, cu, cv);
-  }
 }
 
 // One launch of a tile instance: one block per 32 x 8 tile of every image
 template <bool D21_F32, bool P1_I64, bool LIN_OUT, bool SCREEN, bool FUSE_PROJ>
 static void launch_tile(const void* D11h, const void* D21, const void* p1, void* out, int B, int H, int W,
-                        int dilation_max, int4* olist, int* ocount, const float* cmax, const ProjArgs& pa,
-                        hipStream_t s) {
+                        int dilation_max, const float* cmax, const ProjArgs& pa, hipStream_t s) {
   const int tx = (W + RT_TW - 1) / RT_TW, ty = (H + RT_TH - 1) / RT_TH, nb = tx * ty * B;
   hipLaunchKernelGGL((refine_tile_kernel<D21_F32, P1_I64, LIN_OUT, SCREEN, FUSE_PROJ>), dim3(nb), dim3(RT_THREADS), 0,
-                     s, reinterpret_cast<const h1*>(D11h), D21, p1, out, H, W, dilation_max, tx, tx * ty, nb, olist,
-                     ocount, cmax, pa);
+                     s, reinterpret_cast<const h1*>(D11h), D21, p1, out, H, W, dilation_max, tx, tx * ty, nb, cmax, pa);
 }
 
 }  // namespace m3s
@@ -975,42 +904,24 @@ extern "C" int m3s_refine_tile_ok(int B, int H, int W, int F, int radius, int di
   return 1;
 }
 
-// D21 f32 + p1 int32 -> idx (fused path) or D21 f16 + p1 int64 -> p1_new (reference op).
-// olist/ocount (nullable): deferred-outlier list of >= B*H*W int4 and its counter, zeroed on the
-// stream before this launch. Returns hipErrorNotSupported when the shape is not eligible (the
-// caller falls back to the per-pixel kernels).
+// D21 f32 + p1 int32 -> idx (fused path) or D21 f16 + p1 int64 -> p1_new (reference op). Returns
+// hipErrorNotSupported when the shape is not eligible (the caller falls back to the per-pixel kernels).
 extern "C" hipError_t m3s_launch_refine_tile(const void* D11h, const void* D21, const void* p1, void* out, int B,
                                              int H, int W, int F, int radius, int dilation_max, int fused,
-                                             void* olist, int* ocount, const float* cmax, hipStream_t s) {
+                                             const float* cmax, hipStream_t s) {
   if (!m3s_refine_tile_ok(B, H, W, F, radius, dilation_max)) return hipErrorNotSupported;
-  const m3s::h1* a = reinterpret_cast<const m3s::h1*>(D11h);
-  int4* ol = reinterpret_cast<int4*>(olist);
-  if (ol == nullptr) ocount = nullptr;
   const m3s::ProjArgs none{};
   if (fused && cmax != nullptr)
-    m3s::launch_tile<true, false, true, true, false>(a, D21, p1, out, B, H, W, dilation_max, ol, ocount, cmax, none, s);
+    m3s::launch_tile<true, false, true, true, false>(D11h, D21, p1, out, B, H, W, dilation_max, cmax, none, s);
   else if (fused)
-    m3s::launch_tile<true, false, true, false, false>(a, D21, p1, out, B, H, W, dilation_max, ol, ocount, nullptr,
-                                                      none, s);
+    m3s::launch_tile<true, false, true, false, false>(D11h, D21, p1, out, B, H, W, dilation_max, nullptr, none, s);
   else
-    m3s::launch_tile<false, true, false, false, false>(a, D21, p1, out, B, H, W, dilation_max, ol, ocount, nullptr,
-                                                       none, s);
-  if (ol != nullptr) {
-    // 1024 waves: the list is empty or short once waves score up to RT_INPLACE_MAX outliers in place (a smaller
-    // grid launches and drains faster); pathological inputs (every lane an outlier) take several passes
-    const int ob = 256;
-    if (fused)
-      hipLaunchKernelGGL((m3s::refine_outlier_kernel<true, true>), dim3(ob), dim3(256), 0, s, a, D21, out, H, W, ol,
-                         ocount);
-    else
-      hipLaunchKernelGGL((m3s::refine_outlier_kernel<false, false>), dim3(ob), dim3(256), 0, s, a, D21, out, H, W,
-                         ol, ocount);
-  }
+    m3s::launch_tile<false, true, false, false, false>(D11h, D21, p1, out, B, H, W, dilation_max, nullptr, none, s);
   return hipGetLastError();
 }
 
 // The fused match path's tile launch with the projection search inside (refine_tile_kernel FUSE_PROJ): X21 /
-// idx_init (nullable) -> valid and idx, no p1 buffer, no deferred list. cnorm_part (nullable: unscreened scoring):
+// idx_init (nullable) -> valid and idx, no p1 buffer. cnorm_part (nullable: unscreened scoring):
 // prep's nparts tile partials. hipErrorNotSupported when the shape is not eligible (the caller takes the
 // proj_occlusion + refine launches).
 extern "C" hipError_t m3s_launch_refine_tile_proj(const void* D11h, const float* D21, int64_t* idx_out, uint8_t* valid,
@@ -1024,11 +935,10 @@ extern "C" hipError_t m3s_launch_refine_tile_proj(const void* D11h, const float*
   const m3s::ProjArgs pa{rays9, X11, X21, idx_init, valid, cnorm_part, nparts, max_iter, lambda_init, cost_thresh,
                          dist_thresh};
   if (cnorm_part != nullptr)
-    m3s::launch_tile<true, false, true, true, true>(D11h, D21, nullptr, idx_out, B, H, W, dilation_max, nullptr,
-                                                    nullptr, nullptr, pa, s);
+    m3s::launch_tile<true, false, true, true, true>(D11h, D21, nullptr, idx_out, B, H, W, dilation_max, nullptr, pa, s);
   else
-    m3s::launch_tile<true, false, true, false, true>(D11h, D21, nullptr, idx_out, B, H, W, dilation_max, nullptr,
-                                                     nullptr, nullptr, pa, s);
+    m3s::launch_tile<true, false, true, false, true>(D11h, D21, nullptr, idx_out, B, H, W, dilation_max, nullptr, pa,
+                                                     s);
   return hipGetLastError();
 }
 

@@ -15,8 +15,8 @@ gap, dur = collections.defaultdict(list), collections.defaultdict(list)
 prev_end = None
 for r in rows:
     name = r["Kernel_Name"]
-    short = next((k for k in ("prep_rays", "proj_occlusion", "refine_tile", "refine_outlier", "track_setup",
-                              "gn_loop", "fuse_kernel", "track_init") if k in name), name[:30])
+    short = next((k for k in ("prep_rays", "proj_occlusion", "refine_tile", "track_setup", "gn_loop", "fuse_kernel",
+                              "track_init") if k in name), name[:30])
     s, e = int(r["Start_Timestamp"]), int(r["End_Timestamp"])
     if prev_end is not None:
         gap[short].append((s - prev_end) / 1e3)

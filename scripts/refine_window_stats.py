@@ -63,7 +63,7 @@ def main():
               f"non-inlier px {int((~inl).sum())}")
         for rlim, clim in ((17, 48), (26, 48), (20, 64), (40, 64)):
             print(f"      fits rows<={rlim} cols<={clim}: {np.mean((rows <= rlim) & (cols <= clim)) * 100:.1f}% of tiles")
-        # deferred lanes of the 40 x 64 window when the cover does not fit, by placement rule: bbox middle (shipped),
+        # outlier lanes of the 40 x 64 window when the cover does not fit, by placement rule: bbox middle (shipped),
         # mean inlier centre, tile centre + flow estimate
         RD = 3 * d
         x_lo, x_hi, y_lo, y_hi = mnu - RD, mxu + RD, mnv - RD, mxv + RD
@@ -80,7 +80,7 @@ def main():
             bx = cu - RD - wx0[tile]
             by = cv - RD - wy0[tile]
             lin = (bx >= 0) & (bx + 2 * RD < 64) & (by >= 0) & (by + 2 * RD < 40)
-            print(f"      placement {name:8s}: deferred lanes {int((~lin).sum())}")
+            print(f"      placement {name:8s}: outlier lanes {int((~lin).sum())}")
         # one level (fp32 scores; scan order u outer, v inner; strict '>')
         off = np.arange(-3, 4) * d
         cand_u = np.clip(cu[:, None, None] + off[:, None, None].T.reshape(1, 7, 1), 0, W - 1)

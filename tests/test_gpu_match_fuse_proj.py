@@ -91,37 +91,38 @@ def scattered():
     return (X11, X21, D11, D21, init), O.match(X11, X21, D11, D21, idx_init=init)
 
 
-@pytest.mark.parametrize("inplace", [None, "0"])
-def test_scattered_warm_start(monkeypatch, scattered, inplace):
-    """Every lane a window outlier: in-place scoring (default) and the deferred list with its counter
-    (M3S_REFINE_INPLACE=0, which takes the three-launch path: DESIGN.md section 4)."""
-    if inplace is not None:
-        monkeypatch.setenv("M3S_REFINE_INPLACE", inplace)
-    else:
-        monkeypatch.delenv("M3S_REFINE_INPLACE", raising=False)
+def test_scattered_warm_start(monkeypatch, scattered):
+    """Every lane a window outlier: the unfused and the fused tile instance each score all of them in place."""
     inputs, ref = scattered
     un, fu = _both(monkeypatch, *inputs)
     _assert_same(un, fu, ref)
 
 
-def test_deferred_from_the_coarsest_levels(monkeypatch):
-    """dilation_max = 8: at d = 8 and d = 7 no grid fits the 40-row window (6 d >= 42), so with M3S_REFINE_INPLACE=0
-    every wave defers all its lanes at the first level and refine_outlier_kernel runs levels 8 .. 1. White unit
-    descriptors: each coarse level moves most pixels (the oracle's dilation_max 8 and 7 results differ on 74 % of
-    them; with the smooth synthetic descriptors they are identical), so a dropped or mis-ordered level shows."""
+def test_every_lane_an_outlier_at_the_coarsest_levels(monkeypatch):
+    """dilation_max = 8: at d = 8 and d = 7 a grid spans 6 d + 1 = 49 and 43 rows and the window holds at most 40, so
+    every active lane of every wave is a window outlier at the first two levels and is scored in place, in the unfused
+    and the fused tile instance and in the reference operator's. 16x64 is the smallest image with full tiles in both
+    directions. White unit descriptors: each coarse level moves most pixels (the oracle's dilation_max 8 and 7 results
+    differ on 74 % of them; with the smooth synthetic descriptors they are identical), so a dropped or mis-ordered
+    level shows."""
+    import mast3r_slam_backends as B
     from m3s.config import config
 
     config["matching"]["dilation_max"] = 8
-    X11, X21, _, _ = _pairs(1, 16, 64, seed=60)
+    H, W = 16, 64
+    X11, X21, _, _ = _pairs(1, H, W, seed=60)
     rng = np.random.default_rng(8)
-    D11, D21 = (rng.standard_normal((1, 16, 64, 24)) for _ in range(2))
+    D11, D21 = (rng.standard_normal((1, H, W, 24)) for _ in range(2))
     D11, D21 = ((d / np.linalg.norm(d, axis=-1, keepdims=True)).astype(np.float32) for d in (D11, D21))
-    args = [_dev(X11), _dev(X21), _dev(D11), _dev(D21)]
     ref = O.match(X11, X21, D11, D21, dilation_max=8)
-    monkeypatch.setenv("M3S_REFINE_INPLACE", "0")
-    _assert_same(ref, _run(args))
-    monkeypatch.delenv("M3S_REFINE_INPLACE")
-    _assert_same(ref, _run(args))
+    un, fu = _both(monkeypatch, X11, X21, D11, D21)
+    _assert_same(un, fu, ref)
+    # the reference operator from the oracle's own centres
+    p1 = O.match_diag(X11, X21, D11, D21, dilation_max=8)["p1"]
+    p1 = np.stack((p1 % W, p1 // W), -1).astype(np.int64)
+    (op,) = B.refine_matches(_dev(D11).half(), _dev(D21.reshape(1, H * W, 24)).half(), _dev(p1), 3, 8)
+    op = op.cpu().numpy()
+    np.testing.assert_array_equal(op[..., 0] + W * op[..., 1], ref[0])
 
 
 @pytest.mark.parametrize("max_iter", [0, 1])

@@ -3,7 +3,7 @@ bbox of the inlier centres as minima of packed signed 16-bit pairs and the tile'
 the wave by DPP and permlane swaps (m3s_common.hpp wave_reduce2) instead of LDS permutes.
 
 Every case compares idx and valid, bit for bit, with the CPU oracle (oracle.oracle.match) for the fused default, for
-the exact scan (M3S_REFINE_SCREEN=0) and for the separate projection launch with the deferred-outlier list
+the exact scan (M3S_REFINE_SCREEN=0) and for the separate projection launch with the unfused tile instance
 (M3S_MATCH_FUSE_PROJ=0), and runs the same centres through the reference operator (refine_matches, the int64 p1
 instance of the same level code). No tolerances anywhere.
 
