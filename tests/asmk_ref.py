@@ -90,8 +90,11 @@ class ForwardDb:
 
 
 def rank(scores, k, min_thresh):
-    """torch.topk(scores, min(k, n)) with ties to the lower index, then the ``> min_thresh`` filter."""
-    order = np.lexsort((np.arange(len(scores)), -scores))[:min(k, len(scores))]
+    """torch.topk(scores, min(k, n)): NaN first (the lower index first among them), then descending with ties to the
+    lower index; then the ``> min_thresh`` filter, which no NaN passes."""
+    scores = np.asarray(scores, dtype=np.float64)
+    nan = np.isnan(scores)
+    order = np.lexsort((np.arange(len(scores)), np.where(nan, 0.0, -scores), ~nan))[:min(k, len(scores))]
     return [int(i) for i in order if scores[i] > min_thresh]
 
 
