@@ -39,7 +39,7 @@ const char* m3s_last_error(void);
  * with torch.cuda.synchronize). When enabled, every launch group is bracketed by hipEvents on its
  * own stream under a name: prep_rays, proj_occlusion, refine_lin, track_setup, gn_iters,
  * ba_linearize, ba_solve, map_count, map_voxel, map_write, quantize_topk, asmk_update (the whole fused call, the
- * quantiser's span inside it), rope2d. query synchronises the recorded events. (m3s_match runs the
+ * quantiser's span inside it), rope2d, head_post. query synchronises the recorded events. (m3s_match runs the
  * projection search inside the refine launch where the tile path is taken: refine_lin then covers both and
  * proj_occlusion has no spans, count 0; M3S_MATCH_FUSE_PROJ=0 separates them.) */
 void m3s_timing_enable(int on);
@@ -209,6 +209,41 @@ int m3s_rope2d(int dtype /* 0 f16, 1 f32, 2 bf16 */, void* tokens, int64_t strid
 int m3s_rope2d_prepare(float base, float fwd, int Q, void* stream);
 int m3s_rope2d_table(float base, float fwd, int Q, int P, float* cos_out, float* sin_out);
 int m3s_rope2d_release(void);
+
+/* postprocess(out, depth_mode, conf_mode, desc_dim, desc_mode, two_confs, desc_conf_mode)
+ *   -> pts3d, conf, desc, desc_conf                         thirdparty/mast3r/mast3r/catmlp_dpt_head.py:25-39, with
+ *                                                           the tail of Cat_MLP_LocalFeatures_DPT_Pts3d.forward in
+ *                                                           front (:82-95: transpose, view, pixel_shuffle, cat),
+ *                                                           dust3r/heads/postprocess.py:22-55 (reg_dense_depth,
+ *                                                           reg_dense_conf) inside and the downsample of
+ *                                                           mast3r_slam/mast3r_utils.py:69-78 behind it
+ * One streaming launch, f32 only. Channels of a pixel: 0..2 xyz, 3 the conf logit, 4..4+F-1 the descriptor, 4+F the
+ * desc_conf logit when two_confs (tc = 1, else 0). F in 1..32.
+ * layout M3S_HEAD_CAT: a = out (B, 4+F+tc, H, W) contiguous, the argument of the reference's postprocess; feat unused;
+ * any H, W. layout M3S_HEAD_TOKENS: a = pts (B, 4, H, W), the DPT output, and feat (B, S, (F+tc) 256), the MLP output
+ * before transpose / view / pixel_shuffle, S = (H/16)(W/16): channel c of pixel (y, x) is
+ * feat[b, (y/16)(W/16) + x/16, c 256 + (y%16) 16 + x%16]; H and W multiples of 16 (patch 16 only).
+ * Outputs, contiguous, over the pixels [::step, ::step] (H' = ceil(H/step), W' = ceil(W/step); a stepped-over pixel is
+ * not read): X (B,H',W',3), C (B,H',W'), D (B,H',W',F), Q (B,H',W').
+ * Modes: depth ('exp', -inf, inf); conf and desc_conf ('exp', vmin, vmax), vmin finite and vmax > vmin (inf included;
+ * the desc_conf bounds are read only when two_confs); desc 'norm'. Arithmetic, fp32 in this order without contraction:
+ *   d = sqrt((x x + y y) + z z);  X = (xyz / (d < 1e-8 ? 1e-8 : d)) expm1(d)
+ *   C = float(vmin) + min(exp(l), float(vmax - vmin)), the difference taken in double as Python takes it; Q likewise on
+ *   its own logit and bounds, or C's bits without two_confs
+ *   D = desc / sqrt((s0 + s1) + (s2 + s3)), s_j the squares of channels j, j+4, ... in order; no clamp: a zero
+ *   descriptor gives NaN, as in the reference
+ * NaN propagates as in torch (a NaN logit or coordinate gives NaN; clip there is not fmin / fmax). sqrt and division
+ * are correctly rounded; exp and expm1 are the device library's.
+ * D is written in 16-byte stores when F % 4 == 0 and D is 16-byte aligned, in scalar stores otherwise. The launch is
+ * asynchronous on `stream`; B H W == 0 launches nothing. Everything is validated before the launch. M3S_EINVAL: a bad
+ * layout, F outside 1..32, step < 1, a negative size, TOKENS with H or W not a multiple of 16, an array of 2^31
+ * elements or more (B H W (4+F+tc)), vmax <= vmin or vmin not finite, a null or misaligned pointer with non-empty
+ * work. */
+#define M3S_HEAD_CAT 0
+#define M3S_HEAD_TOKENS 1
+int m3s_head_post(int layout, const float* a, const float* feat, int B, int H, int W, int F, int two_confs, int step,
+                  double conf_vmin, double conf_vmax, double dconf_vmin, double dconf_vmax, float* X, float* C,
+                  float* D, float* Q, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Fused operators (replace stretches of the reference's Python glue)

@@ -2,7 +2,7 @@
 
 Modules: matching (fused dense matcher), tracker (FrameTracker), global_opt (FactorGraph),
 dist_ba (edge-sharded multi-GPU BA), evaluate (map and trajectory export), sim3 (lietorch-compatible Sim3),
-rope (the ViT's RoPE2D module), frame, config, synthetic.
+rope (the ViT's RoPE2D module), head (the dense head's tail: postprocess, head_tail), frame, config, synthetic.
 The drop-in operator modules are the sibling packages ``mast3r_slam_backends`` and ``curope``.
 """
 import os

@@ -35,6 +35,7 @@ class MapConfig(ctypes.Structure):
 
 
 MAP_SOA, MAP_PLY = 0, 1
+HEAD_CAT, HEAD_TOKENS = 0, 1  # m3s_head_post's input layouts
 EINVAL, EHIP, ESPACE = -1, -2, -3
 
 
@@ -141,6 +142,7 @@ _SIGS = {
     "m3s_rope2d_prepare": ([c_float, c_float, c_int, c_void_p], c_int),
     "m3s_rope2d_table": ([c_float, c_float, c_int, c_int, c_void_p, c_void_p], c_int),
     "m3s_rope2d_release": ([], c_int),
+    "m3s_head_post": ([c_int, c_void_p, c_void_p] + [c_int] * 6 + [c_double] * 4 + [c_void_p] * 5, c_int),
     "m3s_peak_fma_f32": ([c_void_p, c_int, c_int, c_void_p], c_int),
     "m3s_match_workspace_size": ([c_int] * 4, c_size_t),
     "m3s_match": ([c_void_p] * 7 + [c_int] * 5 + [c_float] * 3 + [c_int, c_int, c_void_p, c_size_t, c_void_p], c_int),
@@ -228,6 +230,13 @@ def rope2d_table(base, fwd, Q, P=1024):
     check(lib.m3s_rope2d_table(float(base), float(fwd), int(Q), int(P), c_void_p(cos.ctypes.data),
                                c_void_p(sin.ctypes.data)))
     return cos, sin
+
+
+def env_flag(name, default):
+    """A boolean environment toggle, read per call like the library's own (csrc/abi_common.h env_flag): unset ->
+    default, "0" -> off, any other value -> on."""
+    v = os.environ.get(name)
+    return default if v is None else v != "0"
 
 
 def check(rc):

@@ -13,7 +13,11 @@ spawned backend process of ``main.py``):
 * ``mast3r_slam.retrieval_database.RetrievalDatabase`` becomes a subclass of itself with
   ``m3s.retrieval.DatabaseMixin`` in front (``SUBCLASSES``), so ``load_retriever`` (``mast3r_utils.py:50-57``, which
   imports the name from that module) builds a database whose ``update`` runs on the device; the retrieval model and
-  ``prep_features`` stay the reference's.
+  ``prep_features`` stay the reference's;
+* ``mast3r.catmlp_dpt_head.postprocess`` becomes ``m3s.head.postprocess`` and the head class
+  ``Cat_MLP_LocalFeatures_DPT_Pts3d`` a subclass of itself with ``m3s.head.FusedHeadMixin`` in front, so the head the
+  model factory builds (``mast3r_head_factory`` looks both names up in that module when it is called) hands the DPT
+  and MLP outputs to one HIP launch; the convolutions and the MLP stay the reference's.
 
 Nothing of the reference is copied or edited; without the hook directory on the path nothing changes.
 """
@@ -23,9 +27,11 @@ import sys
 
 PATCHES = {"mast3r_slam.config": ("config", "m3s.config"),
            "mast3r_slam.tracker": ("FrameTracker", "m3s.tracker"),
-           "mast3r_slam.global_opt": ("FactorGraph", "m3s.global_opt")}
+           "mast3r_slam.global_opt": ("FactorGraph", "m3s.global_opt"),
+           "mast3r.catmlp_dpt_head": ("postprocess", "m3s.head")}
 # module -> (its class, the module and name of the mixin put in front of it)
-SUBCLASSES = {"mast3r_slam.retrieval_database": ("RetrievalDatabase", "m3s.retrieval", "DatabaseMixin")}
+SUBCLASSES = {"mast3r_slam.retrieval_database": ("RetrievalDatabase", "m3s.retrieval", "DatabaseMixin"),
+              "mast3r.catmlp_dpt_head": ("Cat_MLP_LocalFeatures_DPT_Pts3d", "m3s.head", "FusedHeadMixin")}
 
 
 class _PatchingFinder(importlib.abc.MetaPathFinder):
@@ -52,12 +58,13 @@ class _PatchingFinder(importlib.abc.MetaPathFinder):
                 if name in PATCHES:
                     attr, src = PATCHES[name]
                     setattr(module, attr, getattr(importlib.import_module(src), attr))
-                else:
+                    setattr(module, "_m3s_original_" + attr, True)
+                if name in SUBCLASSES:  # a module may have both: a name replaced and a class subclassed
                     attr, src, mixin = SUBCLASSES[name]
                     base = getattr(module, attr)
                     setattr(module, attr, type(attr, (getattr(importlib.import_module(src), mixin), base),
                                                {"__module__": base.__module__, "__doc__": base.__doc__}))
-                setattr(module, "_m3s_original_" + attr, True)
+                    setattr(module, "_m3s_original_" + attr, True)
 
         spec.loader = _Loader()
         return spec

@@ -32,10 +32,15 @@ def huber(r, k=1.345):
 def asymmetric_inference(model, frame_i, frame_j):
     """X, C, D, Q (2b,H,W,·) of the pair. Models with ``asymmetric_inference`` (synthetic / replayed
     pointmaps) answer directly; the real AsymmetricMASt3R goes through the reference's own ViT helper
-    (``mast3r_utils.py:190-217``, stock PyTorch-ROCm, outside this package's scope)."""
+    (``mast3r_utils.py:190-217``, stock PyTorch-ROCm, outside this package's scope), or with ``M3S_HEAD_FUSED=1``
+    through ``m3s.head.asymmetric_inference``: the same helper with the head tail in one HIP launch per view."""
     fn = getattr(model, "asymmetric_inference", None)
     if fn is not None:
         return fn(frame_i, frame_j)
+    if _lib.env_flag("M3S_HEAD_FUSED", False):
+        from m3s.head import asymmetric_inference as fused_inference
+
+        return fused_inference(model, frame_i, frame_j)
     from mast3r_slam.mast3r_utils import mast3r_asymmetric_inference
 
     return mast3r_asymmetric_inference(model, frame_i, frame_j)
