@@ -39,7 +39,7 @@ const char* m3s_last_error(void);
  * with torch.cuda.synchronize). When enabled, every launch group is bracketed by hipEvents on its
  * own stream under a name: prep_rays, proj_occlusion, refine_lin, track_setup, gn_iters,
  * ba_linearize, ba_solve, map_count, map_voxel, map_write, quantize_topk, asmk_update (the whole fused call, the
- * quantiser's span inside it), rope2d, head_post. query synchronises the recorded events. (m3s_match runs the
+ * quantiser's span inside it), rope2d, head_post, ingest. query synchronises the recorded events. (m3s_match runs the
  * projection search inside the refine launch where the tile path is taken: refine_lin then covers both and
  * proj_occlusion has no spans, count 0; M3S_MATCH_FUSE_PROJ=0 separates them.) */
 void m3s_timing_enable(int on);
@@ -248,6 +248,66 @@ int m3s_head_post(int layout, const float* a, const float* feat, int B, int H, i
 /* ---------------------------------------------------------------------------------------------
  * Fused operators (replace stretches of the reference's Python glue)
  * ------------------------------------------------------------------------------------------- */
+
+/* create_frame -> resize_img: the frame ingest              mast3r_slam/frame.py:111-122,
+ *                                                           mast3r_utils.py:245-289 (Pillow resize, centre crop,
+ *                                                           ImgNorm) and the `/ 255` copy for uimg
+ * From a decoded HWC image to the ViT's input, bit for bit what Pillow's 8-bit resampler and the float tail give.
+ * Geometry (host doubles, S = max(W1, H1)): L = 512 for size 512, L = nearbyint(224 max(W1/H1, H1/W1)) for size 224;
+ * resized (Wr, Hr) = nearbyint(W1 L / S), nearbyint(H1 L / S) (halves to even, as Python's round); filter LANCZOS
+ * (support 3) when S > L, else BICUBIC (a = -0.5, support 2); crop with cx, cy = Wr / 2, Hr / 2 (integer): size 224:
+ * half = min(cx, cy), box (cx-half, cy-half, cx+half, cy+half); size 512: halfw = ((2 cx) / 16) 8,
+ * halfh = ((2 cy) / 16) 8, and halfh = 3 halfw / 4 when Wr == Hr and not square_ok. The transformation is
+ * (W1/Wr, H1/Hr, (Wr-Wc)/2, (Hr-Hc)/2) with (Wc, Hc) the crop's size. An empty crop is M3S_EINVAL.
+ * Coefficients per axis of length in -> out (host fp64): scale = in/out, fs = max(scale, 1), support = filter support
+ * times fs; for output xx: center = (xx + 0.5) scale, xmin = max(int(center - support + 0.5), 0),
+ * n = min(int(center + support + 0.5), in) - xmin, w[x] = filter((x + xmin - center + 0.5) / fs) (as a product with
+ * 1 / fs), divided by their sum in index order when it is not 0, k[x] = int(w 2^22 -+ 0.5) truncated toward zero.
+ * Passes: out = clamp((2^21 + sum k[x] pix[xmin + x]) >> 22, 0, 255) in int32, arithmetic shift; horizontal first into
+ * a uint8 image, then vertical; an axis that keeps its length is copied, not filtered.
+ * Tail per cropped byte u, fp32 with one rounding per operation: img[b, c, y, x] = ((float(u) / 255) - 0.5) / 0.5;
+ * uimg[b, y/ds, x/ds, c] = float(u) / 255 for y % ds == 0 and x % ds == 0 ((B, ceil(Hc/ds), ceil(Wc/ds), 3));
+ * rgb_u8[b, y, x, c] = u. Any of the three outputs may be NULL.
+ * Source: (B, H1, W1, 3), pixels interleaved and contiguous in a row, rows row_stride bytes apart, images
+ * H1 row_stride bytes apart; M3S_INGEST_U8 bytes (any alignment), or M3S_INGEST_F32 floats (4-byte aligned pointer and
+ * row stride) which become bytes as numpy's uint8(x * 255) does on [0, 1]: one fp32 product, truncated, and clamped
+ * to 0..255 outside that range (NaN gives 0).
+ * m3s_ingest_geometry and m3s_ingest_table are host-only; the latter is the code that fills the device tables: xmin
+ * and n of `out` entries, k of out x ksize entries (row xx at k + xx ksize, zero behind its n taps), ksize at least
+ * 2 ceil(support) + 1. m3s_ingest_prepare builds and uploads the two tables of a geometry on the current device if
+ * they are not cached (synchronous on first use: call it before capturing m3s_ingest into a graph);
+ * m3s_ingest_release frees the current device's tables. m3s_ingest launches two kernels on `stream`: the horizontal
+ * pass over the source rows and crop columns the output reads, into the workspace, and the vertical pass with the
+ * tail. M3S_EINVAL: size not 512 or 224, H1 or W1 outside 1..16384, B outside 0..65535, downsample < 1, an empty crop,
+ * a bad dtype, a null source or workspace with work to do, a misaligned float pointer or stride, img or uimg not
+ * 4-byte aligned; M3S_ESPACE: short workspace. B == 0 launches nothing. */
+#define M3S_INGEST_BICUBIC 0
+#define M3S_INGEST_LANCZOS 1
+#define M3S_INGEST_U8 0
+#define M3S_INGEST_F32 1
+typedef struct m3s_ingest_geom {
+  int resized_w, resized_h;                   /* Wr, Hr */
+  int filter;                                 /* M3S_INGEST_BICUBIC / M3S_INGEST_LANCZOS */
+  int crop_x0, crop_y0, crop_x1, crop_y1;     /* the crop box in the resized image */
+  int out_w, out_h;                           /* Wc, Hc */
+  double scale_w, scale_h, half_crop_w, half_crop_h;
+} m3s_ingest_geom;
+typedef struct m3s_ingest_args {
+  const void* src;    /* device */
+  int src_dtype;      /* M3S_INGEST_U8 / M3S_INGEST_F32 */
+  int64_t row_stride; /* bytes */
+  int B, H1, W1;
+  int size, square_ok, downsample;
+  float* img;         /* (B, 3, Hc, Wc), nullable */
+  float* uimg;        /* (B, ceil(Hc/ds), ceil(Wc/ds), 3), nullable */
+  uint8_t* rgb_u8;    /* (B, Hc, Wc, 3), nullable */
+} m3s_ingest_args;
+int m3s_ingest_geometry(int H1, int W1, int size, int square_ok, m3s_ingest_geom* out /* host */);
+int m3s_ingest_table(int in, int out, int filter, int32_t* xmin, int32_t* n, int32_t* k /* host arrays */, int ksize);
+int m3s_ingest_prepare(int H1, int W1, int size, int square_ok, void* stream);
+int m3s_ingest_release(void);
+size_t m3s_ingest_workspace_size(int H1, int W1, int size, int square_ok, int B); /* 0 for a bad geometry */
+int m3s_ingest(const m3s_ingest_args* args /* host */, void* workspace, size_t workspace_bytes, void* stream);
 
 /* match(X11, X21, D11, D21, idx_init) -> (idx_1_to_2, valid_match2)     matching.py:8-90
  * X11, X21 (B,H,W,3) f32; D11, D21 (B,H,W,F) f32 (F % 8 == 0, F in {16,24,32}); idx_init (B,N) i64

@@ -90,6 +90,21 @@ class AsmkResult(ctypes.Structure):
 
 TRACK_OK, TRACK_MAX_ITERS, TRACK_CHOLESKY_FAILED, TRACK_SKIPPED = 1, 2, 3, 4
 
+INGEST_BICUBIC, INGEST_LANCZOS = 0, 1  # m3s_ingest_geom.filter
+INGEST_U8, INGEST_F32 = 0, 1  # m3s_ingest_args.src_dtype
+
+
+class IngestGeom(ctypes.Structure):
+    _fields_ = [("resized_w", c_int), ("resized_h", c_int), ("filter", c_int), ("crop_x0", c_int), ("crop_y0", c_int),
+                ("crop_x1", c_int), ("crop_y1", c_int), ("out_w", c_int), ("out_h", c_int), ("scale_w", c_double),
+                ("scale_h", c_double), ("half_crop_w", c_double), ("half_crop_h", c_double)]
+
+
+class IngestArgs(ctypes.Structure):
+    _fields_ = [("src", c_void_p), ("src_dtype", c_int), ("row_stride", ctypes.c_int64), ("B", c_int), ("H1", c_int),
+                ("W1", c_int), ("size", c_int), ("square_ok", c_int), ("downsample", c_int), ("img", c_void_p),
+                ("uimg", c_void_p), ("rgb_u8", c_void_p)]
+
 # exported entry points and their argtypes (restype int unless noted)
 _SIGS = {
     "m3s_abi_version": ([], c_int),
@@ -143,6 +158,12 @@ _SIGS = {
     "m3s_rope2d_table": ([c_float, c_float, c_int, c_int, c_void_p, c_void_p], c_int),
     "m3s_rope2d_release": ([], c_int),
     "m3s_head_post": ([c_int, c_void_p, c_void_p] + [c_int] * 6 + [c_double] * 4 + [c_void_p] * 5, c_int),
+    "m3s_ingest_geometry": ([c_int] * 4 + [ctypes.POINTER(IngestGeom)], c_int),
+    "m3s_ingest_table": ([c_int] * 3 + [c_void_p] * 3 + [c_int], c_int),
+    "m3s_ingest_prepare": ([c_int] * 4 + [c_void_p], c_int),
+    "m3s_ingest_release": ([], c_int),
+    "m3s_ingest_workspace_size": ([c_int] * 5, c_size_t),
+    "m3s_ingest": ([ctypes.POINTER(IngestArgs), c_void_p, c_size_t, c_void_p], c_int),
     "m3s_peak_fma_f32": ([c_void_p, c_int, c_int, c_void_p], c_int),
     "m3s_match_workspace_size": ([c_int] * 4, c_size_t),
     "m3s_match": ([c_void_p] * 7 + [c_int] * 5 + [c_float] * 3 + [c_int, c_int, c_void_p, c_size_t, c_void_p], c_int),
@@ -230,6 +251,35 @@ def rope2d_table(base, fwd, Q, P=1024):
     check(lib.m3s_rope2d_table(float(base), float(fwd), int(Q), int(P), c_void_p(cos.ctypes.data),
                                c_void_p(sin.ctypes.data)))
     return cos, sin
+
+
+def ingest_geometry(h, w, size=512, square_ok=False):
+    """Host-only: the IngestGeom of a (h, w) source: resized size, filter, crop box, output size, transformation."""
+    lib = load(require_gpu=False)
+    g = IngestGeom()
+    check(lib.m3s_ingest_geometry(int(h), int(w), int(size), int(bool(square_ok)), ctypes.byref(g)))
+    return g
+
+
+def ingest_table(n_in, n_out, filt):
+    """Host-only: (xmin (out), n (out), k (out, ksize)) int32 arrays of one axis of the ingest's resampler, from the
+    host code that fills the device tables of m3s_ingest; ksize = 2 ceil(support) + 1, a row is zero behind its taps."""
+    import math
+
+    import numpy as np
+
+    lib = load(require_gpu=False)
+    n_in, n_out = int(n_in), int(n_out)
+    if n_in < 1 or n_out < 1:
+        raise ValueError("ingest_table: n_in and n_out must be at least 1")
+    support = (3.0 if int(filt) == INGEST_LANCZOS else 2.0) * max(n_in / n_out, 1.0)
+    ksize = int(math.ceil(support)) * 2 + 1
+    xmin = np.empty(n_out, dtype=np.int32)
+    n = np.empty(n_out, dtype=np.int32)
+    k = np.empty((n_out, ksize), dtype=np.int32)
+    check(lib.m3s_ingest_table(n_in, n_out, int(filt), c_void_p(xmin.ctypes.data), c_void_p(n.ctypes.data),
+                               c_void_p(k.ctypes.data), ksize))
+    return xmin, n, k
 
 
 def env_flag(name, default):

@@ -17,7 +17,10 @@ spawned backend process of ``main.py``):
 * ``mast3r.catmlp_dpt_head.postprocess`` becomes ``m3s.head.postprocess`` and the head class
   ``Cat_MLP_LocalFeatures_DPT_Pts3d`` a subclass of itself with ``m3s.head.FusedHeadMixin`` in front, so the head the
   model factory builds (``mast3r_head_factory`` looks both names up in that module when it is called) hands the DPT
-  and MLP outputs to one HIP launch; the convolutions and the MLP stay the reference's.
+  and MLP outputs to one HIP launch; the convolutions and the MLP stay the reference's;
+* ``mast3r_slam.frame.create_frame`` becomes ``m3s.ingest.create_frame`` (``main.py:319`` calls it once per frame; it
+  builds the reference's own ``Frame``): with ``M3S_INGEST_FUSED=1`` the resize, crop and normalisation run in two HIP
+  launches on the uploaded camera image; with the flag unset it is the reference's host statement, bit for bit.
 
 Nothing of the reference is copied or edited; without the hook directory on the path nothing changes.
 """
@@ -28,7 +31,8 @@ import sys
 PATCHES = {"mast3r_slam.config": ("config", "m3s.config"),
            "mast3r_slam.tracker": ("FrameTracker", "m3s.tracker"),
            "mast3r_slam.global_opt": ("FactorGraph", "m3s.global_opt"),
-           "mast3r.catmlp_dpt_head": ("postprocess", "m3s.head")}
+           "mast3r.catmlp_dpt_head": ("postprocess", "m3s.head"),
+           "mast3r_slam.frame": ("create_frame", "m3s.ingest")}
 # module -> (its class, the module and name of the mixin put in front of it)
 SUBCLASSES = {"mast3r_slam.retrieval_database": ("RetrievalDatabase", "m3s.retrieval", "DatabaseMixin"),
               "mast3r.catmlp_dpt_head": ("Cat_MLP_LocalFeatures_DPT_Pts3d", "m3s.head", "FusedHeadMixin")}
