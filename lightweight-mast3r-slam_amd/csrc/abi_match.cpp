@@ -51,8 +51,11 @@ struct MatchWs {
   float* rays9;   // (B,H,W,9) rays + gradients
   void* D11h;     // f16: (B,3,H,W,8) chunk planes on the refine tile path, else (B,H,W,F)
   int* p1;        // (B,N,2) int32
-  float* cpart;   // the refine screen's norm bound, prep's tile partials (m3s_prep_parts)
-  float* cmax;    // ... reduced by the proj launch (refine.hip SCREEN)
+  float* cpart;   // the refine screen's bounds, prep's tile partials: three runs of m3s_prep_parts floats (max
+                  // |c|_2; with the int8 copy also max |c_k| and max |c|_1)
+  float* cmax;    // ... reduced by the proj launch (refine.hip SCREEN): three floats, one per run
+  void* D8;       // int8 screen copy of the descriptors (refine.hip screened_level8): per image (H,W,16) then
+                  // (H,W,8) bytes, 16 bytes of slack behind the last (a row-end DMA lane reads one pixel past it)
 };
 }  // namespace
 
@@ -60,8 +63,9 @@ static size_t match_carve(Carver& c, int B, int H, int W, int F, MatchWs* w) {
   w->rays9 = c.take<float>((size_t)B * H * W * 9);
   w->D11h = c.take<uint16_t>((size_t)B * H * W * F);
   w->p1 = c.take<int>((size_t)B * H * W * 2);
-  w->cpart = c.take<float>((size_t)m3s_prep_parts(B, H, W));
-  w->cmax = c.take<float>(1);
+  w->cpart = c.take<float>((size_t)3 * m3s_prep_parts(B, H, W));
+  w->cmax = c.take<float>(3);
+  w->D8 = c.take<uint8_t>((size_t)B * H * W * 24 + 16);
   return c.off;
 }
 
@@ -89,11 +93,15 @@ extern "C" int m3s_match(const float* X11, const float* X21, const float* D11, c
   // bound-screened refine (refine.hip): prep publishes the descriptor-norm bound; M3S_REFINE_SCREEN=0 scores every
   // candidate with the exact chain instead (same results, bit for bit; read per call so tests can compare both)
   const bool screen = env_flag("M3S_REFINE_SCREEN", true) && planar;
+  // the screen's levels d >= 2 on an int8 copy of the descriptors (refine.hip screened_level8; same results,
+  // bit for bit). M3S_REFINE_SCREEN8=0 keeps the f16 screen at every level and writes no copy
+  const bool screen8 = screen && F == 24 && env_flag("M3S_REFINE_SCREEN8", true);
+  void* const D8 = screen8 ? w.D8 : nullptr;
   {
     Span sp("prep_rays", s);
     // the f16 descriptors: the tile path's chunk planes (+ the screen's tile partials) or the (B,H,W,F) layout
     HIP_TRY(m3s_launch_prep(X11, w.rays9, radius > 0 ? D11 : nullptr, w.D11h, B, H, W, F, planar,
-                            screen ? w.cpart : nullptr, s),
+                            screen ? w.cpart : nullptr, D8, s),
             "match prep launch");
   }
   // the tile path runs the projection search inside the refine launch (refine.hip FUSE_PROJ: two launches per match,
@@ -104,7 +112,7 @@ extern "C" int m3s_match(const float* X11, const float* X21, const float* D11, c
     Span sp("refine_lin", s);
     HIP_TRY(m3s_launch_refine_tile_proj(w.D11h, D21, idx_out, valid_out, w.rays9, X11, X21, idx_init, B, H, W, F, radius,
                                         dilation_max, max_iter, lambda_init, cost_thresh, dist_thresh,
-                                        screen ? w.cpart : nullptr, m3s_prep_parts(B, H, W), s),
+                                        screen ? w.cpart : nullptr, m3s_prep_parts(B, H, W), D8, s),
             "match fused proj + refine launch");
     return M3S_OK;
   }
@@ -112,7 +120,7 @@ extern "C" int m3s_match(const float* X11, const float* X21, const float* D11, c
     Span sp("proj_occlusion", s);
     HIP_TRY(m3s_launch_proj_occlusion(w.rays9, X11, X21, idx_init, w.p1, valid_out, B, H, W, max_iter, lambda_init,
                                       cost_thresh, dist_thresh, w.cpart, m3s_prep_parts(B, H, W),
-                                      screen ? w.cmax : nullptr, s),
+                                      screen ? w.cmax : nullptr, screen8 ? 3 : 1, s),
             "match proj launch");
   }
   // radius == 0: the refine loop is empty and the kernel only writes idx = pixel_to_lin(p1)
@@ -120,7 +128,7 @@ extern "C" int m3s_match(const float* X11, const float* X21, const float* D11, c
   {
     Span sp("refine_lin", s);
     HIP_TRY(m3s_launch_refine_lin(w.D11h, D21, w.p1, idx_out, B, H, W, F, radius, radius > 0 ? dilation_max : 0,
-                                  screen ? w.cmax : nullptr, s),
+                                  screen ? w.cmax : nullptr, D8, s),
             "match refine launch");
   }
   return M3S_OK;

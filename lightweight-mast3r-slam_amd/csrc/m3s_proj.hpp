@@ -35,6 +35,28 @@ __device__ __forceinline__ float reduce_cnorm_wave(const float* __restrict__ par
   return m;
 }
 
+// ... of three runs of nparts partials at once (the int8 screen's: norm, max component, max 1-norm), every load of
+// the three in flight together
+__device__ __forceinline__ void reduce_cnorm3_wave(const float* __restrict__ part, int nparts, float m[3]) {
+  const int lane = threadIdx.x & 63;
+  m[0] = m[1] = m[2] = 0.0f;
+  for (int base = lane; base < nparts; base += 64 * 16) {
+    float v[3][16];
+#pragma unroll
+    for (int r = 0; r < 3; r++)
+#pragma unroll
+      for (int k = 0; k < 16; k++) v[r][k] = part[(size_t)r * nparts + min(base + 64 * k, nparts - 1)];
+#pragma unroll
+    for (int r = 0; r < 3; r++)
+#pragma unroll
+      for (int k = 0; k < 16; k++) m[r] = fmaxf_nan(m[r], v[r][k]);
+  }
+#pragma unroll
+  for (int r = 0; r < 3; r++)
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) m[r] = fmaxf_nan(m[r], __shfl_xor(m[r], off, 64));
+}
+
 // ... into cmax[0], by the first wave of one block of the launch between prep and refine (proj_occlusion)
 __device__ __forceinline__ void reduce_cnorm(const float* __restrict__ part, int nparts, float* __restrict__ cmax) {
   const float m = reduce_cnorm_wave(part, nparts);

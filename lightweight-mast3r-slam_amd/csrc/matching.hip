@@ -26,11 +26,20 @@ __device__ __forceinline__ void desc_load(const float* __restrict__ D11, int b, 
   for (int k = 0; k < 6; k++) v[k] = src[k];
 }
 
-__device__ __forceinline__ float desc_planar(const float4 v[6], h1* __restrict__ D11h, int b, int n, int N) {
+// Q8: also the int8 copy for the refine screen's levels d >= 2 (refine.hip screened_level8), quantised from the f16
+// value so a host restatement is exact: c8 = clamp(rint(127 c_h), -127, 127) (127 c_h is exact in fp32, rint is RNE).
+// Per image two planes: channels 0..15 as (H,W,16) bytes, then channels 16..23 as (H,W,8) bytes, so a window row
+// of either plane is one contiguous run for 16-byte LDS DMA. amax / c1: the pixel's max |c_h,k| and sum |c_h,k|
+// (the int8 bound's inputs; NaN-propagating like the norm).
+template <bool Q8>
+__device__ __forceinline__ float desc_planar(const float4 v[6], h1* __restrict__ D11h, signed char* __restrict__ D8,
+                                             int b, int n, int N, float& amax, float& c1) {
   float ss = 0.0f;
+  amax = c1 = 0.0f;
   if (n < N) {
     const size_t plane = (size_t)N * 8;
     h1* dst = D11h + (size_t)b * 3 * plane + (size_t)n * 8;
+    unsigned w8[6];
 #pragma unroll
     for (int c = 0; c < 3; c++) {
       const float4 v0 = v[2 * c], v1 = v[2 * c + 1];
@@ -38,6 +47,22 @@ __device__ __forceinline__ float desc_planar(const float4 v[6], h1* __restrict__
       *reinterpret_cast<uint4*>(dst + c * plane) = *reinterpret_cast<uint4*>(r);
 #pragma unroll
       for (int k = 0; k < 8; k++) ss += (float)r[k] * (float)r[k];
+      if constexpr (Q8) {
+        w8[2 * c] = w8[2 * c + 1] = 0u;
+#pragma unroll
+        for (int k = 0; k < 8; k++) {
+          const float x = (float)r[k];
+          amax = fmaxf_nan(amax, fabsf(x));
+          c1 += fabsf(x);
+          const int qi = (int)rintf(fminf(fmaxf(127.0f * x, -127.0f), 127.0f));
+          w8[2 * c + (k >> 2)] |= (unsigned)(qi & 0xff) << (8 * (k & 3));
+        }
+      }
+    }
+    if constexpr (Q8) {
+      signed char* d8 = D8 + (size_t)b * N * 24;
+      *reinterpret_cast<uint4*>(d8 + (size_t)n * 16) = uint4{w8[0], w8[1], w8[2], w8[3]};
+      *reinterpret_cast<uint2*>(d8 + (size_t)N * 16 + (size_t)n * 8) = uint2{w8[4], w8[5]};
     }
   }
   return ss;
@@ -51,20 +76,22 @@ __device__ __forceinline__ float desc_planar(const float4 v[6], h1* __restrict__
 // the (B,H,W,F) layout of the per-pixel refine kernels.
 // ------------------------------------------------------------------------------------------
 #define PREP_T 16
-// DMODE: 0 no descriptors, 1 planar (refine tile path), 2 the (B,H,W,F) row layout; a template argument so the
-// planar path's descriptor loads, issued first, cross no branch join (a runtime `if` made the compiler convert them,
-// and so wait for them, right behind the loads)
+// DMODE: 0 no descriptors, 1 planar (refine tile path), 2 the (B,H,W,F) row layout, 3 planar plus the int8 screen copy
+// D8 and its two bound partials (cnorm_part then holds three runs of one float per block: max |c|_2, max |c_k|,
+// max |c|_1); a template argument so the planar path's descriptor loads, issued first, cross no branch join (a
+// runtime `if` made the compiler convert them, and so wait for them, right behind the loads)
 template <int DMODE>
 __global__ void __launch_bounds__(256) prep_rays_kernel(const float* __restrict__ X11, float* __restrict__ rays9,
                                                         const float* __restrict__ D11, h1* __restrict__ D11h, int H,
-                                                        int W, int F, float* __restrict__ cnorm_part) {
+                                                        int W, int F, float* __restrict__ cnorm_part,
+                                                        signed char* __restrict__ D8) {
   __shared__ float tile[(PREP_T + 2) * (PREP_T + 2) * 3];
   const int b = blockIdx.z;
   const int u0 = blockIdx.x * PREP_T, v0 = blockIdx.y * PREP_T;
   const float* Xb = X11 + (size_t)b * H * W * 3;
   const int lx = threadIdx.x % PREP_T, ly = threadIdx.x / PREP_T;
   const int x = u0 + lx, y = v0 + ly;
-  constexpr bool planar_d = DMODE == 1;
+  constexpr bool planar_d = DMODE == 1 || DMODE == 3, q8 = DMODE == 3;
   const int dn = (x < W && y < H) ? y * W + x : H * W;
   // the 18x18 halo: 324 pixels, two per thread at most (256 threads); both loads issued before either is used
   constexpr int HALO = (PREP_T + 2) * (PREP_T + 2);
@@ -135,19 +162,27 @@ __global__ void __launch_bounds__(256) prep_rays_kernel(const float* __restrict_
 #undef T3
   }
   if constexpr (planar_d) {
-    const float ss = desc_planar(dv, D11h, b, dn, H * W);
+    float amax, c1;
+    const float ss = desc_planar<q8>(dv, D11h, D8, b, dn, H * W, amax, c1);
     if (cnorm_part != nullptr) {
       // the tile's max |D11h[pixel]|_2, one partial per block (every block of the fused refine launch reduces them
       // itself; on the three-launch path proj_occlusion does, before refine reads the bound); NaN / inf descriptors give a NaN / inf partial, which switches the screen off for every lane
-      __shared__ float s_max[4];
-      float nmax = sqrtf(ss);
+      constexpr int NP = q8 ? 3 : 1;
+      __shared__ float s_max[NP][4];
+      float pm[3] = {sqrtf(ss), amax, c1};
 #pragma unroll
-      for (int off = 32; off > 0; off >>= 1) nmax = fmaxf_nan(nmax, __shfl_xor(nmax, off, 64));
-      if ((threadIdx.x & 63) == 0) s_max[threadIdx.x >> 6] = nmax;
+      for (int p = 0; p < NP; p++) {
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) pm[p] = fmaxf_nan(pm[p], __shfl_xor(pm[p], off, 64));
+        if ((threadIdx.x & 63) == 0) s_max[p][threadIdx.x >> 6] = pm[p];
+      }
       __syncthreads();
-      if (threadIdx.x == 0)
-        cnorm_part[((size_t)b * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x] =
-            fmaxf_nan(fmaxf_nan(s_max[0], s_max[1]), fmaxf_nan(s_max[2], s_max[3]));
+      if (threadIdx.x < NP) {
+        const int p = threadIdx.x;
+        const size_t nparts = (size_t)gridDim.x * gridDim.y * gridDim.z;
+        cnorm_part[p * nparts + ((size_t)b * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x] =
+            fmaxf_nan(fmaxf_nan(s_max[p][0], s_max[p][1]), fmaxf_nan(s_max[p][2], s_max[p][3]));
+      }
     }
   } else if constexpr (DMODE == 2) {
     // f32 -> f16 of this tile's descriptor rows (B,H,W,F), 4 channels per lane-step (the per-pixel kernels'
@@ -192,9 +227,10 @@ __global__ void __launch_bounds__(256) proj_occlusion_kernel(
     const float* __restrict__ rays, const float* __restrict__ X11, const float* __restrict__ X21,
     const int64_t* __restrict__ idx_init, int* __restrict__ p1, uint8_t* __restrict__ valid, int H, int W,
     int max_iter, float lambda_init, float cost_thresh, float dist_thresh, const float* __restrict__ cnorm_part,
-    int nparts, float* __restrict__ cmax) {
+    int nparts, float* __restrict__ cmax, int nruns) {
   const int N = H * W;
-  if (cmax != nullptr && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x < 64) reduce_cnorm(cnorm_part, nparts, cmax);
+  if (cmax != nullptr && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x < 64)
+    for (int r = 0; r < nruns; r++) reduce_cnorm(cnorm_part + (size_t)r * nparts, nparts, cmax + r);
   // contiguous pixel runs per XCD: each XCD's L2 then holds the rays rows its LM gathers touch
   const int n = xcd_remap(blockIdx.x, gridDim.x) * blockDim.x + threadIdx.x;
   const int b = blockIdx.y;
@@ -340,13 +376,17 @@ __global__ void __launch_bounds__(256) refine_f32_kernel(const float* __restrict
 // launchers (declared in m3s_match.h, called from abi_match.cpp)
 // ------------------------------------------------------------------------------------------
 // D11 (nullable): convert the descriptors too, planar (refine tile path, F = 24; cnorm_part nullable: the tile
-// partials of the screen's norm bound, B * tiles floats) or in the (B,H,W,F) layout (per-pixel refine kernels)
+// partials of the screen's norm bound, B * tiles floats) or in the (B,H,W,F) layout (per-pixel refine kernels).
+// D8 (nullable; needs cnorm_part): the planar path also writes the int8 screen copy (B x 24 N bytes) and cnorm_part
+// holds 3 x B * tiles floats (norm, max component, max 1-norm)
 extern "C" hipError_t m3s_launch_prep(const float* X11, float* rays9, const float* D11, void* D11h, int B, int H,
-                                      int W, int F, int planar, float* cnorm_part, hipStream_t s) {
+                                      int W, int F, int planar, float* cnorm_part, void* D8, hipStream_t s) {
   dim3 grid((W + PREP_T - 1) / PREP_T, (H + PREP_T - 1) / PREP_T, B);
-  auto k = D11 == nullptr ? m3s::prep_rays_kernel<0> : planar ? m3s::prep_rays_kernel<1> : m3s::prep_rays_kernel<2>;
+  auto k = D11 == nullptr ? m3s::prep_rays_kernel<0>
+           : !planar      ? m3s::prep_rays_kernel<2>
+           : (D8 != nullptr && cnorm_part != nullptr) ? m3s::prep_rays_kernel<3> : m3s::prep_rays_kernel<1>;
   hipLaunchKernelGGL(k, grid, dim3(256), 0, s, X11, rays9, D11, reinterpret_cast<m3s::h1*>(D11h), H, W, F,
-                     cnorm_part);
+                     cnorm_part, reinterpret_cast<signed char*>(D8));
   return hipGetLastError();
 }
 
@@ -367,12 +407,14 @@ extern "C" hipError_t m3s_launch_iter_proj(const float* rays, const float* pts, 
 extern "C" hipError_t m3s_launch_proj_occlusion(const float* rays, const float* X11, const float* X21,
                                                 const int64_t* idx_init, int* p1, uint8_t* valid, int B, int H, int W,
                                                 int max_iter, float lambda_init, float cost_thresh, float dist_thresh,
-                                                const float* cnorm_part, int nparts, float* cmax, hipStream_t s) {
+                                                const float* cnorm_part, int nparts, float* cmax, int nruns,
+                                                hipStream_t s) {
   if ((size_t)9 * H * W >= ((size_t)1 << 31)) return hipErrorInvalidValue;  // bilin_sample9's 32-bit offsets
-  // cmax (nullable): one wave reduces prep's tile partials into the refine screen's bound
+  // cmax (nullable): one wave reduces prep's tile partials into the refine screen's bound (nruns = 3 with the int8
+  // screen copy: cmax[0..2] = norm, max component, max 1-norm)
   dim3 grid((H * W + 255) / 256, B);
   hipLaunchKernelGGL(m3s::proj_occlusion_kernel, grid, dim3(256), 0, s, rays, X11, X21, idx_init, p1, valid, H, W,
-                     max_iter, lambda_init, cost_thresh, dist_thresh, cnorm_part, nparts, cmax);
+                     max_iter, lambda_init, cost_thresh, dist_thresh, cnorm_part, nparts, cmax, nruns);
   return hipGetLastError();
 }
 
@@ -394,7 +436,8 @@ extern "C" hipError_t m3s_launch_refine_f16(const void* D11, const void* D21, co
   const m3s::h1* a = reinterpret_cast<const m3s::h1*>(D11);
   const m3s::h1* q = reinterpret_cast<const m3s::h1*>(D21);
   if (N == H * W &&
-      m3s_launch_refine_tile(D11, D21, p1, p1_new, B, H, W, F, radius, dilation_max, 0, nullptr, s) == hipSuccess)
+      m3s_launch_refine_tile(D11, D21, p1, p1_new, B, H, W, F, radius, dilation_max, 0, nullptr, nullptr, s) ==
+          hipSuccess)
     return hipSuccess;  // tiled LDS path (query n is pixel n of the grid)
   return refine_with_F(F, [&](auto f) {
     hipLaunchKernelGGL(m3s::refine_f16_kernel<decltype(f)::value>, grid, dim3(256), 0, s, a, q, p1, p1_new, H, W, N,
@@ -413,12 +456,12 @@ extern "C" hipError_t m3s_launch_refine_f32(const float* D11, const float* D21, 
 
 extern "C" hipError_t m3s_launch_refine_lin(const void* D11h, const float* D21, const int* p1, int64_t* idx_out, int B,
                                             int H, int W, int F, int radius, int dilation_max, const float* cmax,
-                                            hipStream_t s) {
+                                            const void* D8, hipStream_t s) {
   dim3 grid((H * W + 255) / 256, B);
   const m3s::h1* a = reinterpret_cast<const m3s::h1*>(D11h);
   // tiled LDS path exactly when m3s_refine_tile_ok (prep wrote the PLANAR D11h then)
   if (radius > 0 && m3s_refine_tile_ok(B, H, W, F, radius, dilation_max))
-    return m3s_launch_refine_tile(D11h, D21, p1, idx_out, B, H, W, F, radius, dilation_max, 1, cmax, s);
+    return m3s_launch_refine_tile(D11h, D21, p1, idx_out, B, H, W, F, radius, dilation_max, 1, cmax, D8, s);
   return refine_with_F(F, [&](auto f) {
     hipLaunchKernelGGL(m3s::refine_lin_kernel<decltype(f)::value>, grid, dim3(256), 0, s, a, D21, p1, idx_out, H, W,
                        radius, dilation_max);

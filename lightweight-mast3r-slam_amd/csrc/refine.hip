@@ -14,7 +14,9 @@
 //     hide each other's fill latency (measured: faster than double-buffering at two blocks per CU). The fine levels'
 //     covers are small enough for other layouts of the same 40 KiB (bound-screened path): at d = 2 two 26 x 48
 //     chunk buffers (chunk c + 1 streams in while chunk c is screened), at d = 1 all three chunk planes of a 17 x 48
-//     window in one fill, the survivors then rescored from LDS.
+//     window in one fill, the survivors then rescored from LDS. The levels d >= 2 of the fused path screen an
+//     int8 copy of D11 instead (24 B / px, written by prep_rays_kernel; screened_level8): two fills of the 40 x 64
+//     window instead of three, one where the cover fits 30 x 56, and v_dot4c_i32_i8 for half the screen's dots.
 //   * Levels are specialised on d, so every candidate read is one ds_read_b128 with an immediate
 //     offset from a single per-lane base; the 49 running half sums live in registers across the
 //     three chunks (the sum stays sequential over k = 0..23: c10::Half step rounding unchanged).
@@ -48,7 +50,20 @@ constexpr int RT_PROWS = 17, RT_PCOLS = 48, RT_PPLANE = RT_PROWS * RT_PCOLS;
 // double-buffered window (SCREEN, d = 2): two 26-row x 48-column chunk buffers (2 x 19.5 KiB), chunk c + 1 streams in
 // while chunk c is screened (the d = 2 cover is 23 x 45-47 on 97.6 % of the synthetic 512x512 tiles)
 constexpr int RT_DROWS = 26, RT_DBUF = RT_DROWS * RT_PCOLS;
+// int8 windows (SCREEN, d >= 2, screened_level8): 24 B per cell as a 16-channel plane (16 B cells) and an 8-channel
+// plane (8 B cells). The general 40 x 64 window holds one plane at a time (two fills); a cover within 30 x 56 holds
+// both (30 x 56 x 24 B = 39.4 KiB, one fill): the d = 3 and d = 2 covers are 28 x 51 and 23 x 45 at the median
+// (scripts/refine_window_stats.py)
+constexpr int RT_8ROWS = 30, RT_8COLS = 56;
+// the finest level that takes the int8 screen: 2 (its A/B against d >= 3 alone: profiles/refine_screen8_ab.json;
+// -DRT_S8_DMIN=3 builds that variant). At d = 1 the int8 band would hold 5 more survivors per wave at the maximum
+// (profiles/refine_screen8_census.txt): the packed f16 window stays.
+#ifndef RT_S8_DMIN
+#define RT_S8_DMIN 2
+#endif
 static_assert(RT_TH == 2 * RT_WAVES, "two pixel rows per wave");
+static_assert(RT_8ROWS * RT_8COLS * 24 <= RT_ROWS * RT_COLS * 16, "the one-fill int8 window shares the block's window");
+static_assert(RT_8COLS % 2 == 0 && RT_8COLS <= 64 && RT_COLS == 64, "8-byte cells are filled in pairs, two rows per DMA");
 static_assert(3 * RT_PROWS * RT_PCOLS <= RT_ROWS * RT_COLS && 2 * RT_DROWS * RT_PCOLS <= RT_ROWS * RT_COLS,
               "the packed and double-buffered windows share the block's window");
 
@@ -245,6 +260,8 @@ __device__ __forceinline__ void score_chunk(const uint4* base, const h2* q4, h1*
 //   * After the first level the centre candidate (3,3) is the last winner (its score IS the running max) or the
 //     start pixel that did not beat +0: it never wins a strict '>' and is dropped from the survivors.
 //   * |q| cmax > 16384 (overflow range) or non-finite: every in-image candidate survives (exact for all).
+//   * The int8 screen of the levels d >= 2 is the same argument with S8 / 127^2 in place of S_dot2 and B8 = B + E8 in
+//     place of B (E8: the quantisation error of the exact integer dot); restated in front of screen_bound8.
 // seed (chunk 0, a constant at every call site): a[] is written, not accumulated into. The candidate's first product
 // starts from +0 (0 + x: the same bits as accumulating into a zeroed register), so the 49 accumulators are not live
 // in front of chunk 0: zeroed ahead of the fill barrier they cost 98 moves per level (49 to zero them, 49 more where
@@ -362,6 +379,12 @@ struct TileCtx {
   int tcu, tcv; // tile centre + flow estimate: the window's centre when the centres' cover does not fit
   float bq = 0.0f;   // SCREEN: this lane's bound B (0.0125 |q| cmax + 2^-18)
   bool sok = false;  // SCREEN: the bound is usable (|q| cmax <= 16384 and finite)
+  // the int8 screen of the levels d >= RT_S8_DMIN (screened_level8)
+  const signed char* img8 = nullptr;  // this image's int8 planes: (H,W,16) bytes, then (H,W,8)
+  bool s8 = false;    // block-uniform: the copy is there and every |c_h,k| <= 1 (the frame's partials finite)
+  bool sok8 = false;  // this lane's int8 bound is usable (sok, and every |q_h,k| <= 1)
+  float b8 = 0.0f;    // ... the bound B8 = B + E8
+  unsigned q8[6];     // ... and its query, four signed bytes per word, channels in order
 };
 
 // One level's window over D11 (block-uniform) and this lane's column of it
@@ -369,6 +392,7 @@ struct LevelWin {
   int wx0, wy0;       // image coordinates of the window's corner
   int nrows, ncols;   // rows and columns actually filled
   bool packed, dbuf;  // layout: the packed (d = 1) or the double-buffered (d = 2) window, else the general one
+  bool one8;          // int8 levels: both planes in one fill of the 30 x 56 window, else two fills of the general one
   bool col_in;        // this lane's column is filled
   int lane_off;       // ... and its offset in a D11h row, in halves
 };
@@ -447,11 +471,14 @@ __device__ __forceinline__ LevelWin level_window(const TileCtx& t, bool active, 
   // scripts/refine_window_stats.py)
   const int x_lo = mnu - RD, x_hi = mxu + RD, y_lo = mnv - RD, y_hi = mxv + RD;
   LevelWin w;
-  w.packed = w.dbuf = false;  // block-uniform: every input is
+  w.packed = w.dbuf = w.one8 = false;  // block-uniform: every input is
+  if constexpr (SCREEN && PLANAR && D >= RT_S8_DMIN)
+    w.one8 = t.s8 && x_hi - x_lo + 1 <= RT_8COLS && y_hi - y_lo + 1 <= RT_8ROWS;
   if constexpr (SCREEN && D == 1) w.packed = x_hi - x_lo + 1 <= RT_PCOLS && y_hi - y_lo + 1 <= RT_PROWS;
-  if constexpr (SCREEN && D == 2) w.dbuf = x_hi - x_lo + 1 <= RT_PCOLS && y_hi - y_lo + 1 <= RT_DROWS;
-  const int wc = (w.packed || w.dbuf) ? RT_PCOLS : RT_COLS;
-  const int wr = w.packed ? RT_PROWS : (w.dbuf ? RT_DROWS : RT_ROWS);
+  if constexpr (SCREEN && D == 2)
+    w.dbuf = !(PLANAR && D >= RT_S8_DMIN && t.s8) && x_hi - x_lo + 1 <= RT_PCOLS && y_hi - y_lo + 1 <= RT_DROWS;
+  const int wc = (w.packed || w.dbuf) ? RT_PCOLS : (w.one8 ? RT_8COLS : RT_COLS);
+  const int wr = w.packed ? RT_PROWS : (w.dbuf ? RT_DROWS : (w.one8 ? RT_8ROWS : RT_ROWS));
   w.wx0 = (x_hi - x_lo + 1 <= wc) ? x_lo : t.tcu - wc / 2;
   w.wy0 = (y_hi - y_lo + 1 <= wr) ? y_lo : t.tcv - wr / 2;
   // rows and columns actually filled: the bbox cover, clipped to the window (a fine level's cover is ~40 of the 64
@@ -617,6 +644,187 @@ __device__ __forceinline__ void screened_level(const TileCtx& t, const LevelWin&
   }
 }
 
+// ---- the int8 screen of the levels d >= RT_S8_DMIN = 2 (SCREEN + PLANAR) ----
+// The screen score is S8 = sum q8_k c8_k, exact in int32 (v_dot4c_i32_i8: 6 per candidate instead of 12 dot2), over
+// q8 = clamp(rint(127 q_h)), c8 = clamp(rint(127 c_h)) (prep_rays_kernel's copy). With every |q_h,k| <= 1 and
+// |c_h,k| <= 1 no clamp acts, so q_h = q8 / 127 + dq, c_h = c8 / 127 + dc with |dq|, |dc| <= 0.5 / 127, and
+//   |sum q_h c_h - S8 / 127^2| = |sum dq c_h + (q8 / 127) dc| <= E8 = (0.5 / 127) (c1max + |q8|_1 / 127),
+// c1max = max over the image of |c_h|_1 (prep's third partial). B8 = B + E8 bounds |S_half - S8 / 127^2|: B (header
+// comment of screen_chunk) already covers |S_half - S_real|. The proof there carries over with S8 / 127^2 for S_dot2
+// and B8 for B: the winner w has S8[w] / 127^2 >= M - B8 >= Lmax - 2 B8 and > max_score - B8, so the survivors are
+// the candidates with S8 >= 127^2 max(max_score - B8, Lmax - 2 B8). The comparison runs in integers against that
+// threshold rounded down, less one for the fp32 arithmetic that forms it (|.| < 2^20: its error is far below 1):
+// only ever more survivors. The centre drop, the no-survivor skip and the in-image masking are the f16 screen's.
+// A lane with some |q_h,k| > 1 or not finite keeps every in-image candidate (!sok8); a frame with some |c_h,k| > 1
+// or a non-finite partial takes the f16 screen at these levels (t.s8, block-uniform).
+constexpr float RT_K8 = 127.0f * 127.0f;
+// floor to int32, saturating (a lane without a usable bound may hold anything here; its threshold is not used)
+__device__ __forceinline__ int floor_i32(float x) { return (int)floorf(fminf(fmaxf(x, -2.0e9f), 2.0e9f)); }
+
+// the lane's int8 query and bound (after screen_bound); amax, c1max: the frame's max |c_h,k| and max |c_h|_1
+__device__ __forceinline__ void screen_bound8(TileCtx& t, const h2* q, float amax, float c1max) {
+  t.s8 = t.img8 != nullptr && amax <= 1.0f;  // false for NaN; a finite amax <= 1 makes c1max <= 24
+  float qa = 0.0f;
+  int qn1 = 0;
+#pragma unroll
+  for (int k = 0; k < 6; k++) t.q8[k] = 0u;
+#pragma unroll
+  for (int k = 0; k < 24; k++) {
+    const float x = (k & 1) ? (float)q[k >> 1].y : (float)q[k >> 1].x;
+    qa = fmaxf_nan(qa, fabsf(x));
+    const int qi = (int)rintf(fminf(fmaxf(127.0f * x, -127.0f), 127.0f));
+    qn1 += abs(qi);
+    t.q8[k >> 2] |= (unsigned)(qi & 0xff) << (8 * (k & 3));
+  }
+  t.sok8 = t.sok && qa <= 1.0f;
+  // rounded up: c1max is a 24-term fp32 sum
+  t.b8 = t.bq + (0.5f / 127.0f) * (c1max + (float)qn1 * (1.0f / 127.0f)) * 1.001f;
+}
+
+// Rows of the int8 planes into LDS. Plane A (16 B cells): row y at dstA + y * STRIDE, one DMA per row like fill_rows.
+// Plane B (8 B cells): row y at dstB + y * STRIDE / 2 (uint4 units); a lane moves 16 B = two cells, STRIDE / 2 lanes
+// a row, so one DMA (contiguous in LDS) takes two rows. A pair of cells that straddles the image's edge is read
+// where it lies (one pixel before the row's start or behind its end: inside the copy, which has 16 B of slack at its
+// end and plane A in front of plane B), so the cell inside the image holds its own pixel; a pair outside holds any.
+// yA / yB: this wave's first row of either plane (step RT_WAVES rows, 2 RT_WAVES for B)
+template <int STRIDE>
+__device__ __forceinline__ void fill_rows8(const TileCtx& t, const LevelWin& w, uint4* dstA, uint4* dstB, int yA,
+                                           int yB) {
+  constexpr int LPR = STRIDE / 2;  // lanes per plane-B row
+  const size_t N = (size_t)t.H * t.W;
+  if (dstA != nullptr) {
+    for (int y = yA; y < w.nrows; y += RT_WAVES) {
+      const int gy = min(max(w.wy0 + y, 0), t.H - 1);
+      const signed char* rowp = t.img8 + (size_t)gy * t.W * 16;
+      if (w.col_in)
+        __builtin_amdgcn_global_load_lds((gvoid_t)(rowp + 2 * w.lane_off), (lvoid_t)&dstA[y * STRIDE], 16, 0, 0);
+    }
+  }
+  if (dstB != nullptr) {
+    const int h = t.lane / LPR, l = t.lane - h * LPR;
+    const int cc = min(max(w.wx0 + 2 * l, -1), t.W - 1);
+    const bool on = h < 2 && 2 * l < w.ncols;
+    const signed char* pB = t.img8 + N * 16;
+    for (int y = yB; y < w.nrows; y += 2 * RT_WAVES) {
+      const int gy = min(max(w.wy0 + y + h, 0), t.H - 1);
+      const signed char* src = pB + ((ptrdiff_t)gy * t.W + cc) * 8;
+      if (on && y + h < w.nrows)
+        __builtin_amdgcn_global_load_lds((gvoid_t)src, (lvoid_t)&dstB[y * LPR], 16, 0, 0);
+    }
+  }
+}
+
+// 49 candidates x one int8 plane from LDS (NW words a cell: 4 = plane A, which seeds a[]; 2 = plane B); base =
+// candidate (0,0) of this lane in that plane. Same column batching and pinning as screen_chunk.
+template <int D, int STRIDE, int NW>
+__device__ __forceinline__ void screen8_chunk(const void* basev, const unsigned* q8, int* a) {
+  constexpr int G = 7;
+  typedef typename std::conditional<NW == 4, uint4, uint2>::type V;
+  const V* base = reinterpret_cast<const V*>(basev);
+#pragma unroll
+  for (int i = 0; i < G; i++) {
+    V c[G];
+#pragma unroll
+    for (int j = 0; j < G; j++) c[j] = base[j * D * STRIDE + i * D];
+#pragma unroll
+    for (int j = 0; j < G; j++) {
+      const unsigned* cw = reinterpret_cast<const unsigned*>(&c[j]);
+      int s = NW == 4 ? 0 : a[i * G + j];
+#pragma unroll
+      for (int k = 0; k < NW; k++) s = __builtin_amdgcn_sdot4((int)q8[k], (int)cw[k], s, false);
+      a[i * G + j] = s;
+    }
+    int* ac = &a[i * G];
+    asm volatile("" : "+v"(ac[0]), "+v"(ac[1]), "+v"(ac[2]), "+v"(ac[3]), "+v"(ac[4]), "+v"(ac[5]), "+v"(ac[6]));
+    __builtin_amdgcn_sched_barrier(0);
+  }
+}
+
+// screen_mask for the int32 scores: bit c set where a[c] >= T
+__device__ __forceinline__ uint64_t screen_mask8(const int* a, int T) {
+  constexpr int C = 49;
+  unsigned lo = 0u, hi = 0u;
+  unsigned long long s[C];
+#pragma unroll
+  for (int k = 0; k < C + 2; k++) {
+    if (k < C) asm volatile("v_cmp_ge_i32_e64 %0, %1, %2" : "=s"(s[k]) : "v"(a[C - 1 - k]), "v"(T));
+    if (k >= 2) {
+      unsigned long long co;  // the carry-out (dead)
+      if (C - 1 - (k - 2) >= 32)
+        asm volatile("v_addc_co_u32_e64 %0, %1, %0, %0, %2" : "+v"(hi), "=s"(co) : "s"(s[k - 2]));
+      else
+        asm volatile("v_addc_co_u32_e64 %0, %1, %0, %0, %2" : "+v"(lo), "=s"(co) : "s"(s[k - 2]));
+    }
+  }
+  return ((uint64_t)hi << 32) | lo;
+}
+
+// The int8-screened level: fill by layout and screen, integer threshold, mask, exact chains of the survivors from
+// D11h (L2) as in screened_level, re-centre
+template <int D, bool PLANAR>
+__device__ __forceinline__ void screened_level8(const TileCtx& t, const LevelWin& w, const LaneGrid& g, const h2* q,
+                                                int& cu, int& cv, h1& max_score, uint4* lds, bool first) {
+  constexpr int G = 7;
+  const int wid = t.wid, H = t.H, W = t.W;
+  int a[G * G];  // written by plane A's screen
+  __syncthreads();  // the reduction scratch aliases the window: its readers are done
+  rt_prio_from<RT_PRIO_START, RT_PRIO_FILL, D>();
+  if (w.one8) {  // both planes in one fill: plane A's 30 x 56 x 16 B, plane B behind it
+    uint4* ldsB = &lds[RT_8ROWS * RT_8COLS];
+    // plane A's rows wid, wid + 4, ..; plane B's row pairs dealt from the wave that follows A's last row
+    fill_rows8<RT_8COLS>(t, w, lds, ldsB, wid, 2 * ((wid - w.nrows) & (RT_WAVES - 1)));
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    rt_prio_from<RT_PRIO_FILL, RT_PRIO_SCORE, D>();
+    if (g.in) {
+      const int b0 = g.by * RT_8COLS + g.bx;
+      screen8_chunk<D, RT_8COLS, 4>(&lds[b0], &t.q8[0], a);
+      screen8_chunk<D, RT_8COLS, 2>(reinterpret_cast<const uint2*>(ldsB) + b0, &t.q8[4], a);
+    }
+  } else {  // the general window, one plane at a time
+    const int b0 = g.by * RT_COLS + g.bx;
+    fill_rows8<RT_COLS>(t, w, lds, nullptr, wid, 0);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    rt_prio_from<RT_PRIO_FILL, RT_PRIO_SCORE, D>();
+    if (g.in) screen8_chunk<D, RT_COLS, 4>(&lds[b0], &t.q8[0], a);
+    rt_prio_from<RT_PRIO_SCORE, RT_PRIO_FILL, D>();
+    __syncthreads();  // plane A's readers are done
+    fill_rows8<RT_COLS>(t, w, nullptr, lds, 0, 2 * wid);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    rt_prio_from<RT_PRIO_FILL, RT_PRIO_SCORE, D>();
+    if (g.in) screen8_chunk<D, RT_COLS, 2>(reinterpret_cast<const uint2*>(lds) + b0, &t.q8[4], a);
+  }
+  if (g.in) {
+    uint64_t vm = (1ull << (G * G)) - 1ull;  // in-image candidates
+    if (wave_leaves_image<D>(g, H, W)) {
+      vm = in_image_mask<D>(g.u_lo, g.v_lo, H, W);
+#pragma unroll
+      for (int c = 0; c < G * G; c++) a[c] = ((vm >> c) & 1ull) ? a[c] : INT_MIN;
+    }
+    // the level's best over the candidates that can win (screened_level: the centre cannot raise the threshold)
+    int lmax = a[0];
+#pragma unroll
+    for (int c = 1; c < G * G; c++)
+      if (c != G * G / 2) lmax = max(lmax, a[c]);
+    lmax = max(lmax, first ? a[G * G / 2] : INT_MIN);
+    // thresholds, rounded towards more survivors; the wave-uniform no-survivor skip as in screened_level (the second
+    // term never exceeds lmax)
+    const int tms = floor_i32(((float)max_score - t.b8) * RT_K8) - 1;
+    if (__builtin_amdgcn_readfirstlane((int)(__ballot(!t.sok8 || lmax >= tms) != 0ull)) == 0) return;
+    const int T = max(tms, floor_i32((float)lmax - 2.0f * t.b8 * RT_K8) - 1);
+    uint64_t m = screen_mask8(a, T);
+    if (!t.sok8) m = ~0ull;
+    m &= vm;
+    if (!first) m &= ~(1ull << (G * G / 2));
+    stats_survivors<D>(t.lane, m);
+    int bi = -1;
+    exact_survivors<D, PLANAR>(t.img, H, W, q, g.u_lo, g.v_lo, m, max_score, bi);
+    recentre<D>(g, bi, cu, cv);
+  }
+}
+
 // The exact scan's step over the 49 scores, in scan order (u outer, v inner), strict '>'. MASKED: only the candidates
 // of vm take part
 template <bool MASKED>
@@ -667,7 +875,12 @@ __device__ __forceinline__ void refine_level(const TileCtx& t, bool active, cons
   g.by = g.v_lo - w.wy0;
   g.in = active && g.bx >= 0 && g.bx + 2 * RD < w.ncols && g.by >= 0 && g.by + 2 * RD < w.nrows;
   level_outliers<D, PLANAR>(t, active && !g.in, q, cu, cv, max_score);
-  if constexpr (SCREEN)
+  if constexpr (SCREEN && PLANAR && D >= RT_S8_DMIN) {
+    if (t.s8)  // block-uniform
+      screened_level8<D, PLANAR>(t, w, g, q, cu, cv, max_score, lds, first);
+    else
+      screened_level<D, PLANAR>(t, w, g, q, cu, cv, max_score, lds, first);
+  } else if constexpr (SCREEN)
     screened_level<D, PLANAR>(t, w, g, q, cu, cv, max_score, lds, first);
   else
     exact_level<D, PLANAR>(t, w, g, q, cu, cv, max_score, lds);
@@ -708,10 +921,11 @@ struct ProjArgs {
 };
 
 // The FUSE_PROJ prologue: the lane projects its own pixel (centre -> cu, cv), writes valid and leaves the six loads
-// of its raw D21 row (dv) in flight; SCREEN: wave 0 reduces prep's norm partials (cmax_w).
+// of its raw D21 row (dv) in flight; SCREEN: wave 0 reduces prep's norm partials (cmax_w[0]; with the int8 copy also
+// cmax_w[1], cmax_w[2]: max component, max 1-norm).
 template <bool SCREEN>
 __device__ __forceinline__ void proj_prologue(const TileCtx& t, const ProjArgs& pa, const void* D21, int b,
-                                              bool active, size_t bn, int& cu, int& cv, float4* dv, float& cmax_w) {
+                                              bool active, size_t bn, int& cu, int& cv, float4* dv, float* cmax_w) {
   constexpr int F = 24;
   const int H = t.H, W = t.W, N = H * W;
   // the LM gathers and the D21 row loads behind them (until the first level's start sets its own)
@@ -724,7 +938,13 @@ __device__ __forceinline__ void proj_prologue(const TileCtx& t, const ProjArgs& 
   const int64_t i0 = pa.idx_init != nullptr ? pa.idx_init[bnc] : (int64_t)n;
   if constexpr (SCREEN) {
     // reduce_cnorm's loads, in flight beside the pixel's own (4 KB from L2 at 512x512)
-    if (t.wid == 0) cmax_w = reduce_cnorm_wave(pa.cnorm_part, pa.nparts);
+    // (with the int8 copy: the three runs norm, max component, max 1-norm)
+    if (t.wid == 0) {
+      if (t.img8 != nullptr)
+        reduce_cnorm3_wave(pa.cnorm_part, pa.nparts, cmax_w);
+      else
+        cmax_w[0] = reduce_cnorm_wave(pa.cnorm_part, pa.nparts);
+    }
   }
   const float nrm = fmaxf(norm3_ref(x, y, z), 1e-12f);  // F.normalize (matching.py:44)
   const float p[3] = {x / nrm, y / nrm, z / nrm};
@@ -754,11 +974,10 @@ __device__ __forceinline__ void proj_prologue(const TileCtx& t, const ProjArgs& 
 
 // Tile flow estimate, once per tile: the centres move by at most 3d per level, well inside the +-16 px inlier band, so
 // the initial mean serves every level (saves a block reduction per level). Sets t.fu / t.fv and t.tcu / t.tcv.
-// XCHG_CMAX: the same exchange hands wave 0's cmax_w to every wave (the return value).
+// XCHG_CMAX: the same exchange hands wave 0's cmax_w[0..2] to every wave (cmax_b).
 template <bool XCHG_CMAX>
-__device__ __forceinline__ float tile_flow(TileCtx& t, bool active, int cu, int cv, int tx, int ty, float cmax_w,
-                                           int (*s_red)[4]) {
-  float cmax_b = 0.0f;
+__device__ __forceinline__ void tile_flow(TileCtx& t, bool active, int cu, int cv, int tx, int ty,
+                                          const float* cmax_w, float* cmax_b, int (*s_red)[4]) {
   // the two displacement sums by wave_reduce2 (32-bit adds; lane 0 holds the wave's su, lane 32 its sv), the count
   // of active lanes from the ballot
   const int sum = wave_reduce2(active ? cu - t.u_pix : 0, active ? cv - t.v_pix : 0, [](int a, int b) { return a + b; });
@@ -766,10 +985,18 @@ __device__ __forceinline__ float tile_flow(TileCtx& t, bool active, int cu, int 
   if ((t.lane & 31) == 0) s_red[t.wid][t.lane >> 5] = sum;
   if (t.lane == 0) {
     s_red[t.wid][2] = na;
-    if constexpr (XCHG_CMAX) s_red[t.wid][3] = __float_as_int(cmax_w);
+    if constexpr (XCHG_CMAX) {
+      if (t.wid == 0) {
+#pragma unroll
+        for (int r = 0; r < 3; r++) s_red[r][3] = __float_as_int(cmax_w[r]);
+      }
+    }
   }
   __syncthreads();
-  if constexpr (XCHG_CMAX) cmax_b = __int_as_float(__builtin_amdgcn_readfirstlane(s_red[0][3]));
+  if constexpr (XCHG_CMAX) {
+#pragma unroll
+    for (int r = 0; r < 3; r++) cmax_b[r] = __int_as_float(__builtin_amdgcn_readfirstlane(s_red[r][3]));
+  }
   // block-uniform: SGPRs (readfirstlane), not VGPRs live across every level
   int tu = 0, tv = 0, tn = 0;
 #pragma unroll
@@ -783,7 +1010,6 @@ __device__ __forceinline__ float tile_flow(TileCtx& t, bool active, int cu, int 
   t.fv = __builtin_amdgcn_readfirstlane(tv / nall);
   t.tcu = tx * RT_TW + RT_TW / 2 + t.fu;
   t.tcv = ty * RT_TH + RT_TH / 2 + t.fv;
-  return cmax_b;
 }
 
 // SCREEN: the lane's bound B from its query's norm and the descriptor-norm bound cm (t.bq, t.sok; derivation in the
@@ -809,7 +1035,8 @@ template <bool D21_F32, bool P1_I64, bool LIN_OUT, bool SCREEN, bool FUSE_PROJ =
 __global__ void __launch_bounds__(RT_THREADS, RT_MIN_BLOCKS)
     refine_tile_kernel(const h1* __restrict__ D11h, const void* __restrict__ D21, const void* __restrict__ p1v,
                        void* __restrict__ outv, int H, int W, int dilation_max, int tiles_x, int tiles_per_img,
-                       int nblocks, const float* __restrict__ cmaxp, const ProjArgs pa) {
+                       int nblocks, const float* __restrict__ cmaxp, const signed char* __restrict__ D8,
+                       const ProjArgs pa) {
   constexpr int F = 24;
   static_assert(!FUSE_PROJ || (D21_F32 && !P1_I64 && LIN_OUT), "the fused projection feeds the fused match path");
   const unsigned long long stamp_top = bstamp_clock();
@@ -836,10 +1063,13 @@ __global__ void __launch_bounds__(RT_THREADS, RT_MIN_BLOCKS)
   const int N = H * W;
   const size_t bn = (size_t)b * N + (size_t)t.v_pix * W + t.u_pix;
   t.img = D11h + (size_t)b * N * F;
+  if constexpr (SCREEN && LIN_OUT) t.img8 = D8 != nullptr ? D8 + (size_t)b * N * F : nullptr;
   h2 q[F / 2];
   int cu = 0, cv = 0;
   float4 dv[F / 4];   // FUSE_PROJ: the raw D21 row, converted where it is first needed
-  float cmax_w = 0.0f;  // FUSE_PROJ && SCREEN: the descriptor-norm bound, held by wave 0 until the tile-flow exchange
+  // FUSE_PROJ && SCREEN: the descriptor-norm bound (and the int8 screen's two), held by wave 0 until the tile-flow
+  // exchange
+  float cmax_w[3] = {0.0f, 0.0f, 0.0f}, cmax_b[3] = {0.0f, 0.0f, 0.0f};
   if constexpr (FUSE_PROJ) {
     proj_prologue<SCREEN>(t, pa, D21, b, active, bn, cu, cv, dv, cmax_w);
   } else if (active) {
@@ -851,7 +1081,7 @@ __global__ void __launch_bounds__(RT_THREADS, RT_MIN_BLOCKS)
   }
   const unsigned long long stamp_lm = bstamp_clock();  // FUSE_PROJ: the LM phase's end
   // FUSE_PROJ && SCREEN: wave 0's cmax_w, for every wave
-  const float cmax_b = tile_flow<FUSE_PROJ && SCREEN>(t, active, cu, cv, tx, ty, cmax_w, s_red);
+  tile_flow<FUSE_PROJ && SCREEN>(t, active, cu, cv, tx, ty, cmax_w, cmax_b, s_red);
   if constexpr (FUSE_PROJ) {
     // the D21 row, f32 -> f16 (RNE, == torch .half(): load_query's conversion) behind the tile-flow exchange: the
     // loads' latency runs under it
@@ -861,7 +1091,14 @@ __global__ void __launch_bounds__(RT_THREADS, RT_MIN_BLOCKS)
       q[2 * k + 1] = h2{(h1)dv[k].z, (h1)dv[k].w};
     }
   }
-  if constexpr (SCREEN) screen_bound(t, q, FUSE_PROJ ? cmax_b : *cmaxp);
+  if constexpr (SCREEN) {
+    screen_bound(t, q, FUSE_PROJ ? cmax_b[0] : cmaxp[0]);
+    if constexpr (LIN_OUT) {
+      // (cmaxp holds three floats when the copy is there)
+      if (t.img8 != nullptr && dilation_max >= RT_S8_DMIN)
+        screen_bound8(t, q, FUSE_PROJ ? cmax_b[1] : cmaxp[1], FUSE_PROJ ? cmax_b[2] : cmaxp[2]);
+    }
+  }
   bstamp_levels_start(FUSE_PROJ, stamp_top);
   h1 max_score = (h1)0.0f;   // numeric_limits<c10::Half>::min() == +0, never reset between levels
   // the levels as straight-line code (d = dilation_max .. 1) instead of a loop over a switch of the eight inlined level
@@ -888,10 +1125,11 @@ __global__ void __launch_bounds__(RT_THREADS, RT_MIN_BLOCKS)
 // One launch of a tile instance: one block per 32 x 8 tile of every image
 template <bool D21_F32, bool P1_I64, bool LIN_OUT, bool SCREEN, bool FUSE_PROJ>
 static void launch_tile(const void* D11h, const void* D21, const void* p1, void* out, int B, int H, int W,
-                        int dilation_max, const float* cmax, const ProjArgs& pa, hipStream_t s) {
+                        int dilation_max, const float* cmax, const void* D8, const ProjArgs& pa, hipStream_t s) {
   const int tx = (W + RT_TW - 1) / RT_TW, ty = (H + RT_TH - 1) / RT_TH, nb = tx * ty * B;
   hipLaunchKernelGGL((refine_tile_kernel<D21_F32, P1_I64, LIN_OUT, SCREEN, FUSE_PROJ>), dim3(nb), dim3(RT_THREADS), 0,
-                     s, reinterpret_cast<const h1*>(D11h), D21, p1, out, H, W, dilation_max, tx, tx * ty, nb, cmax, pa);
+                     s, reinterpret_cast<const h1*>(D11h), D21, p1, out, H, W, dilation_max, tx, tx * ty, nb, cmax,
+                     reinterpret_cast<const signed char*>(D8), pa);
 }
 
 }  // namespace m3s
@@ -908,15 +1146,17 @@ extern "C" int m3s_refine_tile_ok(int B, int H, int W, int F, int radius, int di
 // hipErrorNotSupported when the shape is not eligible (the caller falls back to the per-pixel kernels).
 extern "C" hipError_t m3s_launch_refine_tile(const void* D11h, const void* D21, const void* p1, void* out, int B,
                                              int H, int W, int F, int radius, int dilation_max, int fused,
-                                             const float* cmax, hipStream_t s) {
+                                             const float* cmax, const void* D8, hipStream_t s) {
   if (!m3s_refine_tile_ok(B, H, W, F, radius, dilation_max)) return hipErrorNotSupported;
   const m3s::ProjArgs none{};
   if (fused && cmax != nullptr)
-    m3s::launch_tile<true, false, true, true, false>(D11h, D21, p1, out, B, H, W, dilation_max, cmax, none, s);
+    m3s::launch_tile<true, false, true, true, false>(D11h, D21, p1, out, B, H, W, dilation_max, cmax, D8, none, s);
   else if (fused)
-    m3s::launch_tile<true, false, true, false, false>(D11h, D21, p1, out, B, H, W, dilation_max, nullptr, none, s);
+    m3s::launch_tile<true, false, true, false, false>(D11h, D21, p1, out, B, H, W, dilation_max, nullptr, nullptr, none,
+                                                      s);
   else
-    m3s::launch_tile<false, true, false, false, false>(D11h, D21, p1, out, B, H, W, dilation_max, nullptr, none, s);
+    m3s::launch_tile<false, true, false, false, false>(D11h, D21, p1, out, B, H, W, dilation_max, nullptr, nullptr, none,
+                                                       s);
   return hipGetLastError();
 }
 
@@ -929,16 +1169,17 @@ extern "C" hipError_t m3s_launch_refine_tile_proj(const void* D11h, const float*
                                                   const int64_t* idx_init, int B, int H, int W, int F, int radius,
                                                   int dilation_max, int max_iter, float lambda_init, float cost_thresh,
                                                   float dist_thresh, const float* cnorm_part, int nparts,
-                                                  hipStream_t s) {
+                                                  const void* D8, hipStream_t s) {
   if (!m3s_refine_tile_ok(B, H, W, F, radius, dilation_max)) return hipErrorNotSupported;
   if ((size_t)9 * H * W >= ((size_t)1 << 31)) return hipErrorNotSupported;  // bilin_sample9's 32-bit offsets
   const m3s::ProjArgs pa{rays9, X11, X21, idx_init, valid, cnorm_part, nparts, max_iter, lambda_init, cost_thresh,
                          dist_thresh};
   if (cnorm_part != nullptr)
-    m3s::launch_tile<true, false, true, true, true>(D11h, D21, nullptr, idx_out, B, H, W, dilation_max, nullptr, pa, s);
+    m3s::launch_tile<true, false, true, true, true>(D11h, D21, nullptr, idx_out, B, H, W, dilation_max, nullptr, D8, pa,
+                                                    s);
   else
-    m3s::launch_tile<true, false, true, false, true>(D11h, D21, nullptr, idx_out, B, H, W, dilation_max, nullptr, pa,
-                                                     s);
+    m3s::launch_tile<true, false, true, false, true>(D11h, D21, nullptr, idx_out, B, H, W, dilation_max, nullptr, nullptr,
+                                                     pa, s);
   return hipGetLastError();
 }
 

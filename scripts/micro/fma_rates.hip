@@ -76,6 +76,9 @@ KERNEL(k_add_f64, double, "v_add_f64 %0, %0, %1")
 KERNEL(k_dot2c_f32_f16, float, "v_dot2c_f32_f16 %0, %1, %1")
 KERNEL(k_dot2_f32_f16, float, "v_dot2_f32_f16 %0, %1, %1, %0")
 KERNEL(k_max3_f32, float, "v_max3_f32 %0, %0, %1, %1")
+// the 8-bit screen's candidate (DESIGN §4 refine): int32 dot of two signed-byte quads, VOP2 accumulate and VOP3P forms
+KERNEL(k_dot4c_i32_i8, int, "v_dot4c_i32_i8 %0, %1, %1")
+KERNEL(k_dot4_i32_i8, int, "v_dot4_i32_i8 %0, %1, %1, %0")
 
 typedef void (*kfn)(void*, unsigned long long*, int);
 
@@ -107,6 +110,7 @@ int main() {
       {"v_fma_f64", (const void*)k_fma_f64, 8},       {"v_add_f64", (const void*)k_add_f64, 8},
       {"v_dot2c_f32_f16", (const void*)k_dot2c_f32_f16, 4}, {"v_dot2_f32_f16", (const void*)k_dot2_f32_f16, 4},
       {"v_max3_f32", (const void*)k_max3_f32, 4},
+      {"v_dot4c_i32_i8", (const void*)k_dot4c_i32_i8, 4}, {"v_dot4_i32_i8", (const void*)k_dot4_i32_i8, 4},
   };
   const int iters = 4000;
   printf("gfx950 VALU issue cost per wave64 instruction per SIMD (median over %d CUs, one block per CU):\n"
