@@ -54,7 +54,7 @@ struct MatchWs {
   float* cpart;   // the refine screen's bounds, prep's tile partials: three runs of m3s_prep_parts floats (max
                   // |c|_2; with the int8 copy also max |c_k| and max |c|_1)
   float* cmax;    // ... reduced by the proj launch (refine.hip SCREEN): three floats, one per run
-  void* D8;       // int8 screen copy of the descriptors (refine.hip screened_level8): per image (H,W,16) then
+  void* D8;       // int8 screen copy of the descriptors (refine.hip ScreenI8): per image (H,W,16) then
                   // (H,W,8) bytes, 16 bytes of slack behind the last (a row-end DMA lane reads one pixel past it)
 };
 }  // namespace
@@ -93,7 +93,7 @@ extern "C" int m3s_match(const float* X11, const float* X21, const float* D11, c
   // bound-screened refine (refine.hip): prep publishes the descriptor-norm bound; M3S_REFINE_SCREEN=0 scores every
   // candidate with the exact chain instead (same results, bit for bit; read per call so tests can compare both)
   const bool screen = env_flag("M3S_REFINE_SCREEN", true) && planar;
-  // the screen's levels d >= 2 on an int8 copy of the descriptors (refine.hip screened_level8; same results,
+  // the screen's levels d >= 2 on an int8 copy of the descriptors (refine.hip ScreenI8; same results,
   // bit for bit). M3S_REFINE_SCREEN8=0 keeps the f16 screen at every level and writes no copy
   const bool screen8 = screen && F == 24 && env_flag("M3S_REFINE_SCREEN8", true);
   void* const D8 = screen8 ? w.D8 : nullptr;

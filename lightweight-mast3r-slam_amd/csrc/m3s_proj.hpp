@@ -16,50 +16,37 @@ __device__ __forceinline__ float norm3_ref(float x, float y, float z) {
   return sqrtf(__builtin_fmaf(z, z, __builtin_fmaf(y, y, x * x)));
 }
 
-// max of the prep partials (the refine screen's descriptor-norm bound) by one wave, every lane gets it
-// (16 loads per lane in flight at once: one at a time, the 1024 partials of a 512x512 image were 16 dependent
+// max of each of R runs of nparts prep partials (the refine screen's descriptor-norm bound; with the int8 screen also
+// the max component and the max 1-norm) by one wave, every lane gets m[0..R)
+// (R x 16 loads per lane in flight at once: one at a time, the 1024 partials of a 512x512 image were 16 dependent
 // round trips in front of the wave's own pixels; the max is order-independent, NaN included, so every wave that
 // reduces the same partials gets the same bits)
-__device__ __forceinline__ float reduce_cnorm_wave(const float* __restrict__ part, int nparts) {
+template <int R>
+__device__ __forceinline__ void reduce_cnorm_wave(const float* __restrict__ part, int nparts, float* m) {
   const int lane = threadIdx.x & 63;
-  float m = 0.0f;
+#pragma unroll
+  for (int r = 0; r < R; r++) m[r] = 0.0f;
   for (int base = lane; base < nparts; base += 64 * 16) {
-    float v[16];
+    float v[R][16];
 #pragma unroll
-    for (int k = 0; k < 16; k++) v[k] = part[min(base + 64 * k, nparts - 1)];
-#pragma unroll
-    for (int k = 0; k < 16; k++) m = fmaxf_nan(m, v[k]);
-  }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) m = fmaxf_nan(m, __shfl_xor(m, off, 64));
-  return m;
-}
-
-// ... of three runs of nparts partials at once (the int8 screen's: norm, max component, max 1-norm), every load of
-// the three in flight together
-__device__ __forceinline__ void reduce_cnorm3_wave(const float* __restrict__ part, int nparts, float m[3]) {
-  const int lane = threadIdx.x & 63;
-  m[0] = m[1] = m[2] = 0.0f;
-  for (int base = lane; base < nparts; base += 64 * 16) {
-    float v[3][16];
-#pragma unroll
-    for (int r = 0; r < 3; r++)
+    for (int r = 0; r < R; r++)
 #pragma unroll
       for (int k = 0; k < 16; k++) v[r][k] = part[(size_t)r * nparts + min(base + 64 * k, nparts - 1)];
 #pragma unroll
-    for (int r = 0; r < 3; r++)
+    for (int r = 0; r < R; r++)
 #pragma unroll
       for (int k = 0; k < 16; k++) m[r] = fmaxf_nan(m[r], v[r][k]);
   }
 #pragma unroll
-  for (int r = 0; r < 3; r++)
+  for (int r = 0; r < R; r++)
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) m[r] = fmaxf_nan(m[r], __shfl_xor(m[r], off, 64));
 }
 
 // ... into cmax[0], by the first wave of one block of the launch between prep and refine (proj_occlusion)
 __device__ __forceinline__ void reduce_cnorm(const float* __restrict__ part, int nparts, float* __restrict__ cmax) {
-  const float m = reduce_cnorm_wave(part, nparts);
+  float m;
+  reduce_cnorm_wave<1>(part, nparts, &m);
   if ((threadIdx.x & 63) == 0) *cmax = m;
 }
 

@@ -26,7 +26,7 @@ __device__ __forceinline__ void desc_load(const float* __restrict__ D11, int b, 
   for (int k = 0; k < 6; k++) v[k] = src[k];
 }
 
-// Q8: also the int8 copy for the refine screen's levels d >= 2 (refine.hip screened_level8), quantised from the f16
+// Q8: also the int8 copy for the refine screen's levels d >= 2 (refine.hip ScreenI8), quantised from the f16
 // value so a host restatement is exact: c8 = clamp(rint(127 c_h), -127, 127) (127 c_h is exact in fp32, rint is RNE).
 // Per image two planes: channels 0..15 as (H,W,16) bytes, then channels 16..23 as (H,W,8) bytes, so a window row
 // of either plane is one contiguous run for 16-byte LDS DMA. amax / c1: the pixel's max |c_h,k| and sum |c_h,k|

@@ -1,35 +1,40 @@
 // LDS-tiled coarse-to-fine descriptor refine for MI355X (gfx950), F = 24, radius 3.
 //
-// Reference semantics: refine_matches_kernel<c10::Half>, /root/reference/mast3r_slam/backend/src/
-// matching_kernels.cu:25-81 — per query pixel, dilation d = dmax..1, a 7x7 grid of stride d around
-// the current centre (u outer, v inner), score = sequential c10::Half sum over 24 channels of
-// half(q_k * c_k), strict '>' against a running max that starts at +0 and is never reset, re-centre
-// after each level.
+// Reference semantics: refine_matches_kernel<c10::Half>, mast3r_slam/backend/src/matching_kernels.cu:25-81 — per
+// query pixel, dilation d = dmax..1, a 7x7 grid of stride d around the current centre (u outer, v inner), score =
+// sequential c10::Half sum over 24 channels of half(q_k * c_k), strict '>' against a running max that starts at +0
+// and is never reset, re-centre after each level.
 //
-// MI355X design: one 32x8 pixel tile per 256-lane block (4 blocks / CU, 40 KiB LDS each).
-//   * Once per tile the block estimates the tile's flow (mean initial centre displacement); per level
-//     it takes the bbox of the centres within 16 px of it, places a 64-column x 40-row window over
-//     bbox +- 3d and streams D11 (f16) into LDS in three 8-channel chunks (16 B / px) with
-//     global_load_lds — one wave-instruction per window row, only the cover's columns. Four resident blocks per CU
-//     hide each other's fill latency (measured: faster than double-buffering at two blocks per CU). The fine levels'
-//     covers are small enough for other layouts of the same 40 KiB (bound-screened path): at d = 2 two 26 x 48
-//     chunk buffers (chunk c + 1 streams in while chunk c is screened), at d = 1 all three chunk planes of a 17 x 48
-//     window in one fill, the survivors then rescored from LDS. The levels d >= 2 of the fused path screen an
-//     int8 copy of D11 instead (24 B / px, written by prep_rays_kernel; screened_level8): two fills of the 40 x 64
-//     window instead of three, one where the cover fits 30 x 56, and v_dot4c_i32_i8 for half the screen's dots.
-//   * Levels are specialised on d, so every candidate read is one ds_read_b128 with an immediate
-//     offset from a single per-lane base; the 49 running half sums live in registers across the
-//     three chunks (the sum stays sequential over k = 0..23: c10::Half step rounding unchanged).
-//   * A lane whose 49 candidates do not fit the window (an outlier centre, a clipped window) is a
-//     window outlier: its wave scores it in place, one outlier at a time (wave_level): 49 lanes
-//     score the 49 candidates from global memory (all loads in flight at once) and a first-maximum
-//     wave arg-max reproduces the sequential strict-'>' scan (the running max only grows from +0).
-//   * Tiles are dealt to XCDs in contiguous runs (bijective remap) so each XCD's 4 MiB L2 holds
-//     its slab of D11.
-//   * On the fused match path the same launch first runs the projection search for the tile's pixels (FUSE_PROJ,
-//     m3s_proj.hpp): no launch and no p1 round trip between the LM search and the levels.
-//   * Every block of a 512x512 launch is resident at once, so the waves' issue priority follows their progress
-//     (rt_prio below: a wave a level behind the others on its SIMD outranks them) and the blocks finish together.
+// The kernel (refine_tile_kernel, at the end of the file): one 32x8 pixel tile per 256-lane block, four blocks per CU
+// with 40 KiB of LDS each (they hide each other's fill latency), tiles dealt to XCDs in contiguous runs so each XCD's
+// 4 MiB L2 holds its slab of D11. FUSE_PROJ instances first run the projection search for the tile's pixels
+// (proj_prologue, m3s_proj.hpp): no launch and no p1 round trip between the LM search and the levels. Once per tile
+// the block estimates the tile's flow (tile_flow); then the levels run as straight-line code, each specialised on d.
+//
+// One level (refine_level):
+//   1. level_window: the bbox of the centres within 16 px of pixel + flow, +- 3d, is the level's cover; the window is
+//      placed over it in one of four layouts of the block's 40 KiB (Layout, layout_rows / layout_cols):
+//        GENERAL  40 x 64 cells of 16 B, one plane at a time    every level; three fills (f16 chunks), two (int8 planes)
+//        PACKED   3 planes of 17 x 48                           f16 screen, d = 1: one fill, survivors rescored from LDS
+//        DBUF     2 buffers of 26 x 48                          f16 screen, d = 2: chunk c + 1 streams in under chunk c
+//        ONE8     30 x 56 cells of 16 B, then 30 x 56 of 8 B    int8 screen: both planes in one fill
+//      a smaller layout is taken where the cover fits it. Fills are LDS DMA, one wave-instruction per window row, only
+//      the cover's columns (fill_rows over a SrcPlane; fill_pairs8 for the int8 copy's 8 B cells).
+//   2. level_outliers: a lane whose 49 candidates do not fit the window is scored in place by its wave, one outlier
+//      at a time (wave_level: 49 lanes, 49 candidates from global memory, a first-maximum wave arg-max).
+//   3. the lanes in the window, by instance and level:
+//        exact_level     (!SCREEN)  all 49 candidates by the c10::Half chain from the window (score_chunk), the 49
+//                        running half sums in registers across the three chunks; every read one ds_read_b128 with an
+//                        immediate offset from a single per-lane base.
+//        screened_level  (SCREEN: the fused path's instances) a cheap screen of the 49 candidates (screen_window ->
+//                        screen_chunk), then screened_tail: threshold, mask (screen_mask), exact chains of the
+//                        survivors (exact_survivors from L2, exact_survivors_lds in the PACKED window), re-centre.
+//                        The screen is the int8 one (ScreenI8) at d >= RT_S8_DMIN = 2 when the frame has the int8 copy
+//                        of D11 (24 B / px, written by prep_rays_kernel) and every component is within +-1, else the
+//                        f16 one (ScreenF16): d = 1, M3S_REFINE_SCREEN8=0, and the frame fallback.
+// Why the screened level returns the sequential scan's result bit for bit is written once, in front of ScreenF16; the
+// int8 screen's part of it (the quantisation error, the integer threshold, the two fallbacks) in front of ScreenI8.
+// Wave issue priorities follow the phase and the level (rt_prio below).
 // Compiled with -ffp-contract=off and -fno-slp-vectorize: each candidate's half sum stays a scalar chain (VOP2
 // v_add_f16 for the even channel, SDWA v_add_f16 for the odd one) instead of the SLP vectoriser pairing two
 // candidates per v_pk_add_f16 behind v_perm / v_pack transposes. Measured issue costs on gfx950 at 4 waves/SIMD
@@ -50,7 +55,7 @@ constexpr int RT_PROWS = 17, RT_PCOLS = 48, RT_PPLANE = RT_PROWS * RT_PCOLS;
 // double-buffered window (SCREEN, d = 2): two 26-row x 48-column chunk buffers (2 x 19.5 KiB), chunk c + 1 streams in
 // while chunk c is screened (the d = 2 cover is 23 x 45-47 on 97.6 % of the synthetic 512x512 tiles)
 constexpr int RT_DROWS = 26, RT_DBUF = RT_DROWS * RT_PCOLS;
-// int8 windows (SCREEN, d >= 2, screened_level8): 24 B per cell as a 16-channel plane (16 B cells) and an 8-channel
+// int8 windows (SCREEN, d >= 2, the int8 screen_window): 24 B per cell as a 16-channel plane (16 B cells) and an 8-channel
 // plane (8 B cells). The general 40 x 64 window holds one plane at a time (two fills); a cover within 30 x 56 holds
 // both (30 x 56 x 24 B = 39.4 KiB, one fill): the d = 3 and d = 2 covers are 28 x 51 and 23 x 45 at the median
 // (scripts/refine_window_stats.py)
@@ -61,6 +66,7 @@ constexpr int RT_8ROWS = 30, RT_8COLS = 56;
 #ifndef RT_S8_DMIN
 #define RT_S8_DMIN 2
 #endif
+static_assert(RT_S8_DMIN >= 2, "d = 1 keeps the packed f16 window");
 static_assert(RT_TH == 2 * RT_WAVES, "two pixel rows per wave");
 static_assert(RT_8ROWS * RT_8COLS * 24 <= RT_ROWS * RT_COLS * 16, "the one-fill int8 window shares the block's window");
 static_assert(RT_8COLS % 2 == 0 && RT_8COLS <= 64 && RT_COLS == 64, "8-byte cells are filled in pairs, two rows per DMA");
@@ -243,69 +249,71 @@ __device__ __forceinline__ void score_chunk(const uint4* base, const h2* q4, h1*
   }
 }
 
-// Bound-screened refine (SCREEN): the level's 49 candidates are first scored by an fp32 dot of the same half operands
-// (v_dot2c_f32_f16: 12 per candidate instead of 24 half products + 24 half adds), then only candidates whose screen
-// score lies within the rounding bound of the level's best are scored by the exact c10::Half chain, in scan order.
-// The result is the sequential scan's, bit for bit:
-//   * |S_half - S_real| <= 24 u P + 24 * 2^-25 for the c10::Half chain (u = 2^-11: 24 product roundings, 23 add
-//     roundings, each <= u times a partial sum <= (1 + 0.013) P), where P = sum |q_k c_k| <= |q|_2 |c|_2, and
-//     |S_dot2 - S_real| <= 12 (3 * 2^-24 P + 2^-36) (measured on gfx950, scripts/micro/dot2_exact.hip: at most
-//     3 fp32 roundings of |a0 b0| + |a1 b1| + |acc| per instruction, 2^-36 absolute with subnormal halves);
-//     so B = 0.0125 |q| cmax + 2^-18 bounds |S_half - S_dot2| (24 u = 0.01172), cmax = max |D11h[pixel]|_2
-//     over the image (prep_rays_kernel).
-//   * The winner w (first candidate in scan order with S_half[w] = M = max S_half, when M beats the running max)
-//     has S_dot2[w] >= M - B >= Lmax - 2B, where Lmax = max over in-image candidates of S_dot2 (M >= S_half[c] >=
-//     S_dot2[c] - B), and S_dot2[w] > max_score - B. A candidate failing either cannot win nor tie the winner,
-//     so the scan over the survivors alone (ascending order, strict '>') returns the full scan's result.
-//   * After the first level the centre candidate (3,3) is the last winner (its score IS the running max) or the
-//     start pixel that did not beat +0: it never wins a strict '>' and is dropped from the survivors.
-//   * |q| cmax > 16384 (overflow range) or non-finite: every in-image candidate survives (exact for all).
-//   * The int8 screen of the levels d >= 2 is the same argument with S8 / 127^2 in place of S_dot2 and B8 = B + E8 in
-//     place of B (E8: the quantisation error of the exact integer dot); restated in front of screen_bound8.
-// seed (chunk 0, a constant at every call site): a[] is written, not accumulated into. The candidate's first product
-// starts from +0 (0 + x: the same bits as accumulating into a zeroed register), so the 49 accumulators are not live
-// in front of chunk 0: zeroed ahead of the fill barrier they cost 98 moves per level (49 to zero them, 49 more where
-// the screen's branch re-materialised them), now the one v_mov 0 the compiler puts in front of each candidate's first
-// two-operand v_dot2c. (It selects v_dot2c for fdot2(q, c, 0) whatever the zero's source; the three-operand
-// v_dot2_f32_f16 with an inline 0 would need inline asm and hand-kept dot -> VALU wait states.)
-template <int D, int STRIDE = RT_COLS>
-__device__ __forceinline__ void screen_chunk(const uint4* base, const h2* q4, float* a, bool seed = false) {
+// One window cell's part of a candidate's screen score (the screens and their proof: in front of screened_tail), the
+// cell c against the query words q, accumulated into s. f16: an 8-channel chunk, four v_dot2c_f32_f16 of the same half
+// operands as the exact chain; int8: the 16-channel plane A (uint4) or the 8-channel plane B (uint2), one
+// v_dot4c_i32_i8 per word, exact in int32.
+__device__ __forceinline__ float cell_dot(const h2* q4, const uint4& c, float s) {
+  const h2* cv = reinterpret_cast<const h2*>(&c);
+#pragma unroll
+  for (int k = 0; k < 4; k++) s = __builtin_amdgcn_fdot2(q4[k], cv[k], s, false);
+  return s;
+}
+template <class V>
+__device__ __forceinline__ int cell_dot(const unsigned* q8, const V& c, int s) {
+  const unsigned* cw = reinterpret_cast<const unsigned*>(&c);
+#pragma unroll
+  for (int k = 0; k < (int)(sizeof(V) / 4); k++) s = __builtin_amdgcn_sdot4((int)q8[k], (int)cw[k], s, false);
+  return s;
+}
+
+// 49 candidates x one chunk or plane of the screen from LDS (cell type V, accumulators A, cell_dot); base = candidate
+// (0,0) of this lane in that plane, STRIDE cells a row.
+// seed (the first chunk or plane, a constant at every call site): a[] is written, not accumulated into. The
+// candidate's first product starts from +0 (0 + x: the same bits as accumulating into a zeroed register), so the 49
+// accumulators are not live in front of it: zeroed ahead of the fill barrier they cost 98 moves per level (49 to zero
+// them, 49 more where the screen's branch re-materialised them), now the one v_mov 0 the compiler puts in front of
+// each candidate's first two-operand v_dot2c. (It selects v_dot2c for fdot2(q, c, 0) whatever the zero's source; the
+// three-operand v_dot2_f32_f16 with an inline 0 would need inline asm and hand-kept dot -> VALU wait states.)
+template <int D, int STRIDE = RT_COLS, class V, class Q, class A>
+__device__ __forceinline__ void screen_chunk(const V* base, const Q* q, A* a, bool seed) {
   constexpr int G = 7;
 #pragma unroll
   for (int i = 0; i < G; i++) {
     // the column's candidate reads in flight together (one LDS latency per column, not per candidate)
-    uint4 c[G];
+    V c[G];
 #pragma unroll
     for (int j = 0; j < G; j++) c[j] = base[j * D * STRIDE + i * D];
 #pragma unroll
-    for (int j = 0; j < G; j++) {
-      const h2* cv = reinterpret_cast<const h2*>(&c[j]);
-      float t = seed ? 0.0f : a[i * G + j];
-#pragma unroll
-      for (int k = 0; k < 4; k++) t = __builtin_amdgcn_fdot2(q4[k], cv[k], t, false);
-      a[i * G + j] = t;
-    }
+    for (int j = 0; j < G; j++) a[i * G + j] = cell_dot(q, c[j], seed ? (A)0 : a[i * G + j]);
     // pin the column's dot products here: otherwise the last chunk's are sunk into the survivor code and all 49
     // candidate loads stay live across it (1000+ spilled VGPRs)
-    float* ac = &a[i * G];
+    A* ac = &a[i * G];
     asm volatile("" : "+v"(ac[0]), "+v"(ac[1]), "+v"(ac[2]), "+v"(ac[3]), "+v"(ac[4]), "+v"(ac[5]), "+v"(ac[6]));
     __builtin_amdgcn_sched_barrier(0);
   }
 }
 
-// bit c set where a[c] >= T (c < 49; NaN never), two VALU per candidate: the compare's lane mask (an SGPR pair) shifted
-// into the mask word by an add-with-carry (m = m + m + carry), candidates in descending order so candidate c lands on
-// bit c. The compiler's select / or / 64-bit shift form took about four per candidate. Each instruction is its own asm
-// statement and the compares run two candidates ahead of the adds: gfx950 needs two wait states between a VALU write
-// of an SGPR and a VALU read of it (the compiler pads v_cmp -> v_cndmask with s_nop 1), and the interleave provides
-// them without nops; the compiler sees every operand, so it pads wherever the distance is short (the last two adds).
-__device__ __forceinline__ uint64_t screen_mask(const float* a, float T) {
+// bit c set where a[c] >= T (c < 49; a float NaN never), two VALU per candidate: the compare's lane mask (an SGPR pair)
+// shifted into the mask word by an add-with-carry (m = m + m + carry), candidates in descending order so candidate c
+// lands on bit c. The compiler's select / or / 64-bit shift form took about four per candidate. Each instruction is its
+// own asm statement and the compares run two candidates ahead of the adds: gfx950 needs two wait states between a VALU
+// write of an SGPR and a VALU read of it (the compiler pads v_cmp -> v_cndmask with s_nop 1), and the interleave
+// provides them without nops; the compiler sees every operand, so it pads wherever the distance is short (the last two
+// adds). A: float (the f16 screen's fp32 scores) or int (the int8 screen's): the compare's opcode is the difference.
+template <class A>
+__device__ __forceinline__ uint64_t screen_mask(const A* a, A T) {
   constexpr int C = 49;
   unsigned lo = 0u, hi = 0u;
   unsigned long long s[C];
 #pragma unroll
   for (int k = 0; k < C + 2; k++) {
-    if (k < C) asm volatile("v_cmp_ge_f32_e64 %0, %1, %2" : "=s"(s[k]) : "v"(a[C - 1 - k]), "v"(T));
+    if (k < C) {
+      if constexpr (std::is_same<A, float>::value)
+        asm volatile("v_cmp_ge_f32_e64 %0, %1, %2" : "=s"(s[k]) : "v"(a[C - 1 - k]), "v"(T));
+      else
+        asm volatile("v_cmp_ge_i32_e64 %0, %1, %2" : "=s"(s[k]) : "v"(a[C - 1 - k]), "v"(T));
+    }
     if (k >= 2) {
       unsigned long long co;  // the carry-out (dead)
       if (C - 1 - (k - 2) >= 32)
@@ -317,9 +325,10 @@ __device__ __forceinline__ uint64_t screen_mask(const float* a, float T) {
   return ((uint64_t)hi << 32) | lo;
 }
 
+
 // exact c10::Half chains of the survivor mask m in ascending scan order, read from D11h (L2); strict '>'. Two
 // survivors per trip: both candidates' loads are in flight before the first chain (one L2 round trip per pair)
-template <int D, bool PLANAR>
+template <int D>
 __device__ __forceinline__ void exact_survivors(const h1* __restrict__ img, int H, int W, const h2* q, int u_lo,
                                                 int v_lo, uint64_t m, h1& max_score, int& bi) {
   while (__ballot(m != 0)) {  // wave-uniform trip count: the lane with the most survivors
@@ -335,8 +344,8 @@ __device__ __forceinline__ void exact_survivors(const h1* __restrict__ img, int 
     for (int k = 0; k < 2; k++) {
       if (c[k] >= 0) {
         const int i = c[k] / 7, j = c[k] - 7 * i;
-        load_chunks<PLANAR>(pix_ptr<PLANAR>(img, (size_t)(v_lo + j * D) * W + (u_lo + i * D)), (size_t)H * W, x[k][0],
-                            x[k][1], x[k][2]);
+        load_chunks<true>(pix_ptr<true>(img, (size_t)(v_lo + j * D) * W + (u_lo + i * D)), (size_t)H * W, x[k][0],
+                          x[k][1], x[k][2]);
       }
     }
     rt_prio_from<RT_PRIO_SURV, RT_PRIO_SCORE, D>();
@@ -351,7 +360,7 @@ __device__ __forceinline__ void exact_survivors(const h1* __restrict__ img, int 
 // serialise the fill of chunk c + 1 behind the screen of chunk c; the explicit vmcnt(0) + barrier order it instead.
 // One wait state between the M0 write and the DMA (the compiler's own sequences keep one there too).
 // lds_addr: the row's LDS byte address (wave-uniform)
-__device__ __forceinline__ void lds_dma_row(const h1* g, unsigned lds_addr) {
+__device__ __forceinline__ void lds_dma_row(const char* g, unsigned lds_addr) {
   const unsigned m0 = __builtin_amdgcn_readfirstlane(lds_addr);
   // M0 is an operand ({m0}): the compiler writes it itself right before the asm and knows its value (it also sets M0
   // for its own global_load_lds); the s_nop is the wait state between that M0 write and the DMA that reads it
@@ -372,6 +381,15 @@ __device__ __forceinline__ void exact_survivors_lds(const uint4* base, const h2*
   }
 }
 
+// The int8 screen's state (set by screen_bound8; the derivation is in front of ScreenI8)
+struct Int8Screen {
+  const signed char* img = nullptr;  // this image's int8 planes: A (H,W,16) bytes, then B (H,W,8)
+  bool on = false;   // block-uniform: the copy is there and every |c_h,k| <= 1 (the frame's partials finite)
+  bool sok = false;  // this lane's int8 bound is usable (TileCtx::sok, and every |q_h,k| <= 1)
+  float b = 0.0f;    // ... the bound B8 = B + E8
+  unsigned q[6];     // ... and its query, four signed bytes per word, channels in order
+};
+
 struct TileCtx {
   const h1* img;
   int H, W, lane, wid, u_pix, v_pix;
@@ -379,22 +397,25 @@ struct TileCtx {
   int tcu, tcv; // tile centre + flow estimate: the window's centre when the centres' cover does not fit
   float bq = 0.0f;   // SCREEN: this lane's bound B (0.0125 |q| cmax + 2^-18)
   bool sok = false;  // SCREEN: the bound is usable (|q| cmax <= 16384 and finite)
-  // the int8 screen of the levels d >= RT_S8_DMIN (screened_level8)
-  const signed char* img8 = nullptr;  // this image's int8 planes: (H,W,16) bytes, then (H,W,8)
-  bool s8 = false;    // block-uniform: the copy is there and every |c_h,k| <= 1 (the frame's partials finite)
-  bool sok8 = false;  // this lane's int8 bound is usable (sok, and every |q_h,k| <= 1)
-  float b8 = 0.0f;    // ... the bound B8 = B + E8
-  unsigned q8[6];     // ... and its query, four signed bytes per word, channels in order
+  Int8Screen i8;     // SCREEN: the int8 screen of the levels d >= RT_S8_DMIN
 };
+
+// How a level lays its window out in the block's 40 KiB (the header comment has the table)
+enum class Layout { GENERAL, PACKED, DBUF, ONE8 };
+constexpr int layout_rows(Layout l) {
+  return l == Layout::PACKED ? RT_PROWS : l == Layout::DBUF ? RT_DROWS : l == Layout::ONE8 ? RT_8ROWS : RT_ROWS;
+}
+constexpr int layout_cols(Layout l) {
+  return l == Layout::PACKED || l == Layout::DBUF ? RT_PCOLS : l == Layout::ONE8 ? RT_8COLS : RT_COLS;
+}
 
 // One level's window over D11 (block-uniform) and this lane's column of it
 struct LevelWin {
-  int wx0, wy0;       // image coordinates of the window's corner
-  int nrows, ncols;   // rows and columns actually filled
-  bool packed, dbuf;  // layout: the packed (d = 1) or the double-buffered (d = 2) window, else the general one
-  bool one8;          // int8 levels: both planes in one fill of the 30 x 56 window, else two fills of the general one
-  bool col_in;        // this lane's column is filled
-  int lane_off;       // ... and its offset in a D11h row, in halves
+  int wx0, wy0;      // image coordinates of the window's corner
+  int nrows, ncols;  // rows and columns actually filled
+  Layout layout;
+  bool col_in;       // this lane's column is filled
+  int lane_off;      // ... and its offset in a row of a 16 B-per-pixel plane (D11h's: 48 B when not PLANAR), in bytes
 };
 
 // This lane's 7x7 candidate grid at one level
@@ -412,21 +433,36 @@ __device__ __forceinline__ void recentre(const LaneGrid& g, int bi, int& cu, int
   }
 }
 
-// Rows y0, y0 + RT_WAVES, .. < w.nrows of one 8-channel chunk plane into LDS, dst + y * stride (uint4 units): one DMA
-// (64 lanes x 16 B) per window row, only the cover's columns. The row base (and the chunk plane) is wave-uniform
-// (scalar), the column offset per lane. ASM_DMA: lds_dma_row instead of the builtin (the double-buffered window).
-template <bool PLANAR, bool ASM_DMA>
-__device__ __forceinline__ void fill_rows(const TileCtx& t, const LevelWin& w, uint4* dst, int stride, int chunk,
-                                          int y0) {
-  const size_t cstride = PLANAR ? (size_t)t.H * t.W * 8 : 8, rstride = (size_t)t.W * (PLANAR ? 8 : 24);
+// A plane of a level's source that holds 16 B of a pixel's channels, as a fill reads it: one of D11h's three
+// 8-channel f16 chunks, or the int8 copy's 16-channel plane A
+struct SrcPlane {
+  const char* base;  // the image's row 0 in this plane (wave-uniform)
+  size_t row_bytes;  // from one image row to the next
+  int lane_bytes;    // this lane's window column in a row
+};
+template <bool PLANAR>
+__device__ __forceinline__ SrcPlane chunk_plane(const TileCtx& t, const LevelWin& w, int chunk) {
+  return {reinterpret_cast<const char*>(t.img + chunk * (PLANAR ? (size_t)t.H * t.W * 8 : 8)),
+          (size_t)t.W * (PLANAR ? 16 : 48), w.lane_off};
+}
+__device__ __forceinline__ SrcPlane int8_plane_a(const TileCtx& t, const LevelWin& w) {
+  return {reinterpret_cast<const char*>(t.i8.img), (size_t)t.W * 16, w.lane_off};
+}
+
+// Rows y0, y0 + RT_WAVES, .. < w.nrows of one source plane into LDS, dst + y * stride (uint4 units): one DMA (64 lanes
+// x 16 B) per window row, only the cover's columns. The row base is wave-uniform (scalar), the column offset per
+// lane. ASM_DMA: lds_dma_row instead of the builtin (the double-buffered window).
+template <bool ASM_DMA>
+__device__ __forceinline__ void fill_rows(const TileCtx& t, const LevelWin& w, const SrcPlane& p, uint4* dst,
+                                          int stride, int y0) {
   for (int y = y0; y < w.nrows; y += RT_WAVES) {
     const int gy = min(max(w.wy0 + y, 0), t.H - 1);
-    const h1* rowp = t.img + (size_t)gy * rstride + chunk * cstride;
+    const char* rowp = p.base + (size_t)gy * p.row_bytes;
     if (w.col_in) {
       if constexpr (ASM_DMA)
-        lds_dma_row(rowp + w.lane_off, (unsigned)(uintptr_t)(lvoid_t)&dst[y * stride]);
+        lds_dma_row(rowp + p.lane_bytes, (unsigned)(uintptr_t)(lvoid_t)&dst[y * stride]);
       else
-        __builtin_amdgcn_global_load_lds((gvoid_t)(rowp + w.lane_off), (lvoid_t)&dst[y * stride], 16, 0, 0);
+        __builtin_amdgcn_global_load_lds((gvoid_t)(rowp + p.lane_bytes), (lvoid_t)&dst[y * stride], 16, 0, 0);
     }
   }
 }
@@ -471,14 +507,18 @@ __device__ __forceinline__ LevelWin level_window(const TileCtx& t, bool active, 
   // scripts/refine_window_stats.py)
   const int x_lo = mnu - RD, x_hi = mxu + RD, y_lo = mnv - RD, y_hi = mxv + RD;
   LevelWin w;
-  w.packed = w.dbuf = w.one8 = false;  // block-uniform: every input is
-  if constexpr (SCREEN && PLANAR && D >= RT_S8_DMIN)
-    w.one8 = t.s8 && x_hi - x_lo + 1 <= RT_8COLS && y_hi - y_lo + 1 <= RT_8ROWS;
-  if constexpr (SCREEN && D == 1) w.packed = x_hi - x_lo + 1 <= RT_PCOLS && y_hi - y_lo + 1 <= RT_PROWS;
-  if constexpr (SCREEN && D == 2)
-    w.dbuf = !(PLANAR && D >= RT_S8_DMIN && t.s8) && x_hi - x_lo + 1 <= RT_PCOLS && y_hi - y_lo + 1 <= RT_DROWS;
-  const int wc = (w.packed || w.dbuf) ? RT_PCOLS : (w.one8 ? RT_8COLS : RT_COLS);
-  const int wr = w.packed ? RT_PROWS : (w.dbuf ? RT_DROWS : (w.one8 ? RT_8ROWS : RT_ROWS));
+  // the level's smaller layout where the cover fits it, else the general window (block-uniform: every input is)
+  const auto fits = [&](Layout l) { return x_hi - x_lo + 1 <= layout_cols(l) && y_hi - y_lo + 1 <= layout_rows(l); };
+  w.layout = Layout::GENERAL;
+  if constexpr (SCREEN) {
+    if (D >= RT_S8_DMIN && t.i8.on)
+      w.layout = fits(Layout::ONE8) ? Layout::ONE8 : Layout::GENERAL;
+    else if (D == 1 && fits(Layout::PACKED))
+      w.layout = Layout::PACKED;
+    else if (D == 2 && fits(Layout::DBUF))
+      w.layout = Layout::DBUF;
+  }
+  const int wc = layout_cols(w.layout), wr = layout_rows(w.layout);
   w.wx0 = (x_hi - x_lo + 1 <= wc) ? x_lo : t.tcu - wc / 2;
   w.wy0 = (y_hi - y_lo + 1 <= wr) ? y_lo : t.tcv - wr / 2;
   // rows and columns actually filled: the bbox cover, clipped to the window (a fine level's cover is ~40 of the 64
@@ -486,7 +526,7 @@ __device__ __forceinline__ LevelWin level_window(const TileCtx& t, bool active, 
   w.nrows = min(wr, y_hi - w.wy0 + 1);
   w.ncols = min(wc, x_hi - w.wx0 + 1);
   w.col_in = lane < w.ncols;
-  w.lane_off = min(max(w.wx0 + lane, 0), t.W - 1) * (PLANAR ? 8 : 24);
+  w.lane_off = min(max(w.wx0 + lane, 0), t.W - 1) * (PLANAR ? 16 : 48);
   return w;
 }
 
@@ -533,7 +573,7 @@ __device__ __forceinline__ void general_window(const TileCtx& t, const LevelWin&
       rt_prio_from<RT_PRIO_SCORE, RT_PRIO_FILL, D>();
       __syncthreads();  // previous chunk's readers are done
     }
-    fill_rows<PLANAR, false>(t, w, lds, RT_COLS, chunk, t.wid);
+    fill_rows<false>(t, w, chunk_plane<PLANAR>(t, w, chunk), lds, RT_COLS, t.wid);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     rt_prio_from<RT_PRIO_FILL, RT_PRIO_SCORE, D>();
@@ -558,22 +598,153 @@ __device__ __forceinline__ bool wave_leaves_image(const LaneGrid& g, int H, int 
   return __ballot(g.in && !(g.u_lo >= 0 && g.u_lo + 6 * D < W && g.v_lo >= 0 && g.v_lo + 6 * D < H)) != 0;
 }
 
-// The screened level (header comment of screen_chunk): fill by layout and screen, threshold, mask, exact chains of
-// the survivors, re-centre
-template <int D, bool PLANAR>
-__device__ __forceinline__ void screened_level(const TileCtx& t, const LevelWin& w, const LaneGrid& g, const h2* q,
-                                               int& cu, int& cv, h1& max_score, uint4* lds, bool first) {
-  constexpr int G = 7;
-  const int wid = t.wid, H = t.H, W = t.W;
-  float a[G * G];  // written by chunk 0's screen (seed): no zeroing
-  __syncthreads();  // the reduction scratch aliases the window: its readers are done
-  rt_prio_from<RT_PRIO_START, RT_PRIO_FILL, D>();
+// ---- the screened level (SCREEN) ----
+// The level's 49 candidates are first scored by a cheap screen, then only candidates whose screen score lies within
+// the rounding bound of the level's best are scored by the exact c10::Half chain, in scan order. Two screens share
+// everything but the score: the f16 screen, an fp32 dot of the same half operands (v_dot2c_f32_f16: 12 per candidate
+// instead of 24 half products + 24 half adds), and the int8 screen of the levels d >= RT_S8_DMIN (derived from this
+// one in front of ScreenI8). The result is the sequential scan's, bit for bit:
+//   * |S_half - S_real| <= 24 u P + 24 * 2^-25 for the c10::Half chain (u = 2^-11: 24 product roundings, 23 add
+//     roundings, each <= u times a partial sum <= (1 + 0.013) P), where P = sum |q_k c_k| <= |q|_2 |c|_2, and
+//     |S_dot2 - S_real| <= 12 (3 * 2^-24 P + 2^-36) (measured on gfx950, scripts/micro/dot2_exact.hip: at most
+//     3 fp32 roundings of |a0 b0| + |a1 b1| + |acc| per instruction, 2^-36 absolute with subnormal halves);
+//     so B = 0.0125 |q| cmax + 2^-18 bounds |S_half - S_dot2| (24 u = 0.01172), cmax = max |D11h[pixel]|_2
+//     over the image (prep_rays_kernel).
+//   * The winner w (first candidate in scan order with S_half[w] = M = max S_half, when M beats the running max)
+//     has S_dot2[w] >= M - B >= Lmax - 2B, where Lmax = max over in-image candidates of S_dot2 (M >= S_half[c] >=
+//     S_dot2[c] - B), and S_dot2[w] > max_score - B. A candidate failing either cannot win nor tie the winner,
+//     so the scan over the survivors alone (ascending order, strict '>') returns the full scan's result.
+//   * After the first level the centre candidate (3,3) is the last winner (its score IS the running max) or the
+//     start pixel that did not beat +0: it never wins a strict '>' and is dropped from the survivors.
+//   * |q| cmax > 16384 (overflow range) or non-finite: every in-image candidate survives (exact for all).
+// A screen kind gives screened_tail the accumulator type with its "never wins" value, the lane's usable-bound flag, and
+// the two terms of the threshold T = max(tms, tlm(Lmax)) in the accumulator's units.
+struct ScreenF16 {
+  typedef float acc_t;
+  static __device__ __forceinline__ float never() { return -INFINITY; }
+  static __device__ __forceinline__ bool usable(const TileCtx& t) { return t.sok; }
+  static __device__ __forceinline__ float tms(const TileCtx& t, h1 max_score) { return (float)max_score - t.bq; }
+  static __device__ __forceinline__ float tlm(const TileCtx& t, float lmax) { return lmax - 2.0f * t.bq; }
+};
+
+// the lane's bound B from its query's norm and the descriptor-norm bound cm (t.bq, t.sok)
+__device__ __forceinline__ void screen_bound(TileCtx& t, const h2* q, float cm) {
+  float qq = 0.0f;
+#pragma unroll
+  for (int k = 0; k < 12; k++) qq = __builtin_amdgcn_fdot2(q[k], q[k], qq, false);
+  const float pq = sqrtf(qq) * cm * 1.001f;  // |q|_2 |c|_2 bound, rounded up
+  t.sok = pq <= 16384.0f;                         // false for NaN / inf
+  t.bq = t.sok ? 0.0125f * pq + 0x1p-18f : 0.0f;
+}
+
+// The int8 screen. The screen score is S8 = sum q8_k c8_k, exact in int32 (v_dot4c_i32_i8: 6 per candidate instead of
+// 12 dot2), over q8 = clamp(rint(127 q_h)), c8 = clamp(rint(127 c_h)) (prep_rays_kernel's copy). With every
+// |q_h,k| <= 1 and |c_h,k| <= 1 no clamp acts, so q_h = q8 / 127 + dq, c_h = c8 / 127 + dc with |dq|, |dc| <=
+// 0.5 / 127, and
+//   |sum q_h c_h - S8 / 127^2| = |sum dq c_h + (q8 / 127) dc| <= E8 = (0.5 / 127) (c1max + |q8|_1 / 127),
+// c1max = max over the image of |c_h|_1 (prep's third partial). B8 = B + E8 bounds |S_half - S8 / 127^2|: B already
+// covers |S_half - S_real|. The proof above carries over with S8 / 127^2 for S_dot2 and B8 for B: the winner w has
+// S8[w] / 127^2 >= M - B8 >= Lmax - 2 B8 and > max_score - B8, so the survivors are the candidates with
+// S8 >= 127^2 max(max_score - B8, Lmax - 2 B8). The comparison runs in integers against that threshold rounded down,
+// less one for the fp32 arithmetic that forms it (|.| < 2^20: its error is far below 1): only ever more survivors.
+// A lane with some |q_h,k| > 1 or not finite keeps every in-image candidate (!i8.sok); a frame with some |c_h,k| > 1
+// or a non-finite partial takes the f16 screen at these levels (!i8.on, block-uniform).
+constexpr float RT_K8 = 127.0f * 127.0f;
+// floor to int32, saturating (a lane without a usable bound may hold anything here; its threshold is not used)
+__device__ __forceinline__ int floor_i32(float x) { return (int)floorf(fminf(fmaxf(x, -2.0e9f), 2.0e9f)); }
+struct ScreenI8 {
+  typedef int acc_t;
+  static __device__ __forceinline__ int never() { return INT_MIN; }
+  static __device__ __forceinline__ bool usable(const TileCtx& t) { return t.i8.sok; }
+  static __device__ __forceinline__ int tms(const TileCtx& t, h1 max_score) {
+    return floor_i32(((float)max_score - t.i8.b) * RT_K8) - 1;
+  }
+  static __device__ __forceinline__ int tlm(const TileCtx& t, int lmax) {
+    return floor_i32((float)lmax - 2.0f * t.i8.b * RT_K8) - 1;
+  }
+};
+
+// the lane's int8 query and bound (after screen_bound); amax, c1max: the frame's max |c_h,k| and max |c_h|_1
+__device__ __forceinline__ void screen_bound8(TileCtx& t, const h2* q, float amax, float c1max) {
+  Int8Screen& s = t.i8;
+  s.on = s.img != nullptr && amax <= 1.0f;  // false for NaN; a finite amax <= 1 makes c1max <= 24
+  float qa = 0.0f;
+  int qn1 = 0;
+#pragma unroll
+  for (int k = 0; k < 6; k++) s.q[k] = 0u;
+#pragma unroll
+  for (int k = 0; k < 24; k++) {
+    const float x = (k & 1) ? (float)q[k >> 1].y : (float)q[k >> 1].x;
+    qa = fmaxf_nan(qa, fabsf(x));
+    const int qi = (int)rintf(fminf(fmaxf(127.0f * x, -127.0f), 127.0f));
+    qn1 += abs(qi);
+    s.q[k >> 2] |= (unsigned)(qi & 0xff) << (8 * (k & 3));
+  }
+  s.sok = t.sok && qa <= 1.0f;
+  // rounded up: c1max is a 24-term fp32 sum
+  s.b = t.bq + (0.5f / 127.0f) * (c1max + (float)qn1 * (1.0f / 127.0f)) * 1.001f;
+}
+
+__device__ __forceinline__ float max_of(float a, float b) { return fmaxf(a, b); }
+__device__ __forceinline__ int max_of(int a, int b) { return max(a, b); }
+
+// Everything of a screened level behind the screen, for the lanes whose grid lies in the window (a[]: their 49 screen
+// scores): the in-image mask, the level's best, the threshold, the no-survivor skip, the mask word, the exact chains
+// of the survivors and the re-centre. K: ScreenF16 or ScreenI8.
+template <int D, class K>
+__device__ __forceinline__ void screened_tail(const TileCtx& t, const LevelWin& w, const LaneGrid& g, const h2* q,
+                                              typename K::acc_t* a, int& cu, int& cv, h1& max_score, const uint4* lds,
+                                              bool first) {
+  typedef typename K::acc_t A;
+  constexpr int G = 7, CENTRE = G * G / 2;
+  const int H = t.H, W = t.W;
+  uint64_t vm = (1ull << (G * G)) - 1ull;  // in-image candidates
+  if (wave_leaves_image<D>(g, H, W)) {
+    vm = in_image_mask<D>(g.u_lo, g.v_lo, H, W);
+    // out-of-image candidates scored clamped window pixels: they take no part in the level's best (nor survive)
+#pragma unroll
+    for (int c = 0; c < G * G; c++) a[c] = ((vm >> c) & 1ull) ? a[c] : K::never();
+  }
+  // the level's best over the candidates that can win: after the first level the centre is dropped from the
+  // survivors (below), and it cannot raise T either: its exact score is the running max or a start pixel's <= +0,
+  // so a[centre] - 2B <= max_score - B, the other term of T
+  A lmax = a[0];
+#pragma unroll
+  for (int c = 1; c < G * G; c++)
+    if (c != CENTRE) lmax = max_of(lmax, a[c]);
+  lmax = max_of(lmax, first ? a[CENTRE] : K::never());
+  // No lane of the wave can hold a survivor: the mask, the survivor loop and the re-centre are skipped as one
+  // wave-uniform branch. A lane's mask is non-empty exactly when lmax >= max_score - B: lmax is one of its
+  // candidates' a[c] and never below lmax - 2B, so it clears T = max(max_score - B, lmax - 2B) iff it clears the
+  // first term, and no candidate clears a T that lmax does not (a NaN lmax fails both tests). A lane without a
+  // usable bound (every candidate survives) keeps the wave out of the skip.
+  const A tms = K::tms(t, max_score);
+  if (__builtin_amdgcn_readfirstlane((int)(__ballot(!K::usable(t) || lmax >= tms) != 0ull)) == 0) return;
+  const A T = max_of(tms, K::tlm(t, lmax));
+  uint64_t m = screen_mask(a, T);
+  if (!K::usable(t)) m = ~0ull;
+  m &= vm;
+  if (!first) m &= ~(1ull << CENTRE);
+  stats_survivors<D>(t.lane, m);
+  int bi = -1;
+  if (D == 1 && w.layout == Layout::PACKED)  // the survivors' chunks are resident
+    exact_survivors_lds<D>(&lds[g.by * RT_PCOLS + g.bx], q, m, max_score, bi);
+  else
+    exact_survivors<D>(t.img, H, W, q, g.u_lo, g.v_lo, m, max_score, bi);
+  recentre<D>(g, bi, cu, cv);
+}
+
+// The f16 screen of one level: fill by layout, and the 49 screen scores a[] of the lanes whose grid lies in the window
+template <int D>
+__device__ __forceinline__ void screen_window(const TileCtx& t, const LevelWin& w, const LaneGrid& g, const h2* q,
+                                              uint4* lds, float* a) {
+  const int wid = t.wid;
   const int b0 = g.by * RT_PCOLS + g.bx;  // candidate (0, 0) in the 48-column layouts
-  if (w.packed) {  // (d = 1 only) the three chunk planes in one fill
+  if (D == 1 && w.layout == Layout::PACKED) {  // the three chunk planes in one fill
     // row r = chunk * nrows + y of the 3 * nrows goes to wave r % RT_WAVES: an even deal whatever nrows is
     for (int chunk = 0; chunk < 3; chunk++)
-      fill_rows<PLANAR, false>(t, w, &lds[chunk * RT_PPLANE], RT_PCOLS, chunk,
-                               (wid - chunk * w.nrows) & (RT_WAVES - 1));
+      fill_rows<false>(t, w, chunk_plane<true>(t, w, chunk), &lds[chunk * RT_PPLANE], RT_PCOLS,
+                       (wid - chunk * w.nrows) & (RT_WAVES - 1));
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     rt_prio_from<RT_PRIO_FILL, RT_PRIO_SCORE, D>();
@@ -582,8 +753,8 @@ __device__ __forceinline__ void screened_level(const TileCtx& t, const LevelWin&
       for (int chunk = 0; chunk < 3; chunk++)
         screen_chunk<D, RT_PCOLS>(&lds[chunk * RT_PPLANE + b0], &q[chunk * 4], a, chunk == 0);
     }
-  } else if (w.dbuf) {  // (d = 2 only) chunk c + 1 lands in the other buffer while chunk c is screened
-    fill_rows<PLANAR, true>(t, w, lds, RT_PCOLS, 0, wid);
+  } else if (D == 2 && w.layout == Layout::DBUF) {  // chunk c + 1 lands in the other buffer while chunk c is screened
+    fill_rows<true>(t, w, chunk_plane<true>(t, w, 0), lds, RT_PCOLS, wid);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     // the same wait as a builtin: the compiler's wait model (blind to the asm) learns that none of its own loads
     // (a previous level's survivor loads, spill reloads) is still in flight, so it places no vmcnt(0) of its own
@@ -592,7 +763,8 @@ __device__ __forceinline__ void screened_level(const TileCtx& t, const LevelWin&
     __syncthreads();
 #pragma unroll
     for (int chunk = 0; chunk < 3; chunk++) {  // chunk is screened in buffer chunk & 1
-      if (chunk < 2) fill_rows<PLANAR, true>(t, w, &lds[((chunk + 1) & 1) * RT_DBUF], RT_PCOLS, chunk + 1, wid);
+      if (chunk < 2)
+        fill_rows<true>(t, w, chunk_plane<true>(t, w, chunk + 1), &lds[((chunk + 1) & 1) * RT_DBUF], RT_PCOLS, wid);
       rt_prio_from<RT_PRIO_FILL, RT_PRIO_SCORE, D>();
       if (g.in) screen_chunk<D, RT_PCOLS>(&lds[(chunk & 1) * RT_DBUF + b0], &q[chunk * 4], a, chunk == 0);
       if (chunk < 2) {
@@ -602,228 +774,78 @@ __device__ __forceinline__ void screened_level(const TileCtx& t, const LevelWin&
       }
     }
   } else {
-    general_window<D, PLANAR>(t, w, lds, g.in, [&](int chunk) {
+    general_window<D, true>(t, w, lds, g.in, [&](int chunk) {
       screen_chunk<D>(&lds[g.by * RT_COLS + g.bx], &q[chunk * 4], a, chunk == 0);
     });
   }
-  if (g.in) {
-    uint64_t vm = (1ull << (G * G)) - 1ull;  // in-image candidates
-    if (wave_leaves_image<D>(g, H, W)) {
-      vm = in_image_mask<D>(g.u_lo, g.v_lo, H, W);
-      // out-of-image candidates scored clamped window pixels: they take no part in the level's best (nor survive)
-#pragma unroll
-      for (int c = 0; c < G * G; c++) a[c] = ((vm >> c) & 1ull) ? a[c] : -INFINITY;
-    }
-    // the level's best over the candidates that can win: after the first level the centre is dropped from the
-    // survivors (below), and it cannot raise T either: its exact score is the running max or a start pixel's <= +0,
-    // so a[centre] - 2B <= max_score - B, the other term of T
-    float lmax = a[0];
-#pragma unroll
-    for (int c = 1; c < G * G; c++)
-      if (c != G * G / 2) lmax = fmaxf(lmax, a[c]);
-    lmax = fmaxf(lmax, first ? a[G * G / 2] : -INFINITY);
-    // No lane of the wave can hold a survivor: the mask, the survivor loop and the re-centre are skipped as one
-    // wave-uniform branch. A lane's mask is non-empty exactly when lmax >= max_score - B: lmax is one of its
-    // candidates' a[c] and never below lmax - 2B, so it clears T = max(max_score - B, lmax - 2B) iff it clears the
-    // first term, and no candidate clears a T that lmax does not (a NaN lmax fails both tests). A lane without a
-    // usable bound (!sok: every candidate survives) keeps the wave out of the skip.
-    const float tms = (float)max_score - t.bq;
-    if (__builtin_amdgcn_readfirstlane((int)(__ballot(!t.sok || lmax >= tms) != 0ull)) == 0) return;
-    const float T = fmaxf(tms, lmax - 2.0f * t.bq);
-    uint64_t m = screen_mask(a, T);
-    if (!t.sok) m = ~0ull;
-    m &= vm;
-    if (!first) m &= ~(1ull << (G * G / 2));
-    stats_survivors<D>(t.lane, m);
-    int bi = -1;
-    if (w.packed)
-      exact_survivors_lds<D>(&lds[b0], q, m, max_score, bi);
-    else
-      exact_survivors<D, PLANAR>(t.img, H, W, q, g.u_lo, g.v_lo, m, max_score, bi);
-    recentre<D>(g, bi, cu, cv);
-  }
 }
 
-// ---- the int8 screen of the levels d >= RT_S8_DMIN = 2 (SCREEN + PLANAR) ----
-// The screen score is S8 = sum q8_k c8_k, exact in int32 (v_dot4c_i32_i8: 6 per candidate instead of 12 dot2), over
-// q8 = clamp(rint(127 q_h)), c8 = clamp(rint(127 c_h)) (prep_rays_kernel's copy). With every |q_h,k| <= 1 and
-// |c_h,k| <= 1 no clamp acts, so q_h = q8 / 127 + dq, c_h = c8 / 127 + dc with |dq|, |dc| <= 0.5 / 127, and
-//   |sum q_h c_h - S8 / 127^2| = |sum dq c_h + (q8 / 127) dc| <= E8 = (0.5 / 127) (c1max + |q8|_1 / 127),
-// c1max = max over the image of |c_h|_1 (prep's third partial). B8 = B + E8 bounds |S_half - S8 / 127^2|: B (header
-// comment of screen_chunk) already covers |S_half - S_real|. The proof there carries over with S8 / 127^2 for S_dot2
-// and B8 for B: the winner w has S8[w] / 127^2 >= M - B8 >= Lmax - 2 B8 and > max_score - B8, so the survivors are
-// the candidates with S8 >= 127^2 max(max_score - B8, Lmax - 2 B8). The comparison runs in integers against that
-// threshold rounded down, less one for the fp32 arithmetic that forms it (|.| < 2^20: its error is far below 1):
-// only ever more survivors. The centre drop, the no-survivor skip and the in-image masking are the f16 screen's.
-// A lane with some |q_h,k| > 1 or not finite keeps every in-image candidate (!sok8); a frame with some |c_h,k| > 1
-// or a non-finite partial takes the f16 screen at these levels (t.s8, block-uniform).
-constexpr float RT_K8 = 127.0f * 127.0f;
-// floor to int32, saturating (a lane without a usable bound may hold anything here; its threshold is not used)
-__device__ __forceinline__ int floor_i32(float x) { return (int)floorf(fminf(fmaxf(x, -2.0e9f), 2.0e9f)); }
-
-// the lane's int8 query and bound (after screen_bound); amax, c1max: the frame's max |c_h,k| and max |c_h|_1
-__device__ __forceinline__ void screen_bound8(TileCtx& t, const h2* q, float amax, float c1max) {
-  t.s8 = t.img8 != nullptr && amax <= 1.0f;  // false for NaN; a finite amax <= 1 makes c1max <= 24
-  float qa = 0.0f;
-  int qn1 = 0;
-#pragma unroll
-  for (int k = 0; k < 6; k++) t.q8[k] = 0u;
-#pragma unroll
-  for (int k = 0; k < 24; k++) {
-    const float x = (k & 1) ? (float)q[k >> 1].y : (float)q[k >> 1].x;
-    qa = fmaxf_nan(qa, fabsf(x));
-    const int qi = (int)rintf(fminf(fmaxf(127.0f * x, -127.0f), 127.0f));
-    qn1 += abs(qi);
-    t.q8[k >> 2] |= (unsigned)(qi & 0xff) << (8 * (k & 3));
-  }
-  t.sok8 = t.sok && qa <= 1.0f;
-  // rounded up: c1max is a 24-term fp32 sum
-  t.b8 = t.bq + (0.5f / 127.0f) * (c1max + (float)qn1 * (1.0f / 127.0f)) * 1.001f;
-}
-
-// Rows of the int8 planes into LDS. Plane A (16 B cells): row y at dstA + y * STRIDE, one DMA per row like fill_rows.
-// Plane B (8 B cells): row y at dstB + y * STRIDE / 2 (uint4 units); a lane moves 16 B = two cells, STRIDE / 2 lanes
-// a row, so one DMA (contiguous in LDS) takes two rows. A pair of cells that straddles the image's edge is read
-// where it lies (one pixel before the row's start or behind its end: inside the copy, which has 16 B of slack at its
-// end and plane A in front of plane B), so the cell inside the image holds its own pixel; a pair outside holds any.
-// yA / yB: this wave's first row of either plane (step RT_WAVES rows, 2 RT_WAVES for B)
+// Rows of the int8 copy's plane B (8 B cells) into LDS: row y at dst + y * STRIDE / 2 (uint4 units); a lane moves
+// 16 B = two cells, STRIDE / 2 lanes a row, so one DMA (contiguous in LDS) takes two rows. A pair of cells that
+// straddles the image's edge is read where it lies (one pixel before the row's start or behind its end: inside the
+// copy, which has 16 B of slack at its end and plane A in front of plane B), so the cell inside the image holds its own
+// pixel; a pair outside holds any. y0: this wave's first row (step 2 RT_WAVES rows)
 template <int STRIDE>
-__device__ __forceinline__ void fill_rows8(const TileCtx& t, const LevelWin& w, uint4* dstA, uint4* dstB, int yA,
-                                           int yB) {
-  constexpr int LPR = STRIDE / 2;  // lanes per plane-B row
-  const size_t N = (size_t)t.H * t.W;
-  if (dstA != nullptr) {
-    for (int y = yA; y < w.nrows; y += RT_WAVES) {
-      const int gy = min(max(w.wy0 + y, 0), t.H - 1);
-      const signed char* rowp = t.img8 + (size_t)gy * t.W * 16;
-      if (w.col_in)
-        __builtin_amdgcn_global_load_lds((gvoid_t)(rowp + 2 * w.lane_off), (lvoid_t)&dstA[y * STRIDE], 16, 0, 0);
-    }
-  }
-  if (dstB != nullptr) {
-    const int h = t.lane / LPR, l = t.lane - h * LPR;
-    const int cc = min(max(w.wx0 + 2 * l, -1), t.W - 1);
-    const bool on = h < 2 && 2 * l < w.ncols;
-    const signed char* pB = t.img8 + N * 16;
-    for (int y = yB; y < w.nrows; y += 2 * RT_WAVES) {
-      const int gy = min(max(w.wy0 + y + h, 0), t.H - 1);
-      const signed char* src = pB + ((ptrdiff_t)gy * t.W + cc) * 8;
-      if (on && y + h < w.nrows)
-        __builtin_amdgcn_global_load_lds((gvoid_t)src, (lvoid_t)&dstB[y * LPR], 16, 0, 0);
-    }
+__device__ __forceinline__ void fill_pairs8(const TileCtx& t, const LevelWin& w, uint4* dst, int y0) {
+  constexpr int LPR = STRIDE / 2;  // lanes per row
+  const int h = t.lane / LPR, l = t.lane - h * LPR;
+  const int cc = min(max(w.wx0 + 2 * l, -1), t.W - 1);
+  const bool on = h < 2 && 2 * l < w.ncols;
+  const signed char* pB = t.i8.img + (size_t)t.H * t.W * 16;
+  for (int y = y0; y < w.nrows; y += 2 * RT_WAVES) {
+    const int gy = min(max(w.wy0 + y + h, 0), t.H - 1);
+    const signed char* src = pB + ((ptrdiff_t)gy * t.W + cc) * 8;
+    if (on && y + h < w.nrows) __builtin_amdgcn_global_load_lds((gvoid_t)src, (lvoid_t)&dst[y * LPR], 16, 0, 0);
   }
 }
 
-// 49 candidates x one int8 plane from LDS (NW words a cell: 4 = plane A, which seeds a[]; 2 = plane B); base =
-// candidate (0,0) of this lane in that plane. Same column batching and pinning as screen_chunk.
-template <int D, int STRIDE, int NW>
-__device__ __forceinline__ void screen8_chunk(const void* basev, const unsigned* q8, int* a) {
-  constexpr int G = 7;
-  typedef typename std::conditional<NW == 4, uint4, uint2>::type V;
-  const V* base = reinterpret_cast<const V*>(basev);
-#pragma unroll
-  for (int i = 0; i < G; i++) {
-    V c[G];
-#pragma unroll
-    for (int j = 0; j < G; j++) c[j] = base[j * D * STRIDE + i * D];
-#pragma unroll
-    for (int j = 0; j < G; j++) {
-      const unsigned* cw = reinterpret_cast<const unsigned*>(&c[j]);
-      int s = NW == 4 ? 0 : a[i * G + j];
-#pragma unroll
-      for (int k = 0; k < NW; k++) s = __builtin_amdgcn_sdot4((int)q8[k], (int)cw[k], s, false);
-      a[i * G + j] = s;
-    }
-    int* ac = &a[i * G];
-    asm volatile("" : "+v"(ac[0]), "+v"(ac[1]), "+v"(ac[2]), "+v"(ac[3]), "+v"(ac[4]), "+v"(ac[5]), "+v"(ac[6]));
-    __builtin_amdgcn_sched_barrier(0);
-  }
-}
-
-// screen_mask for the int32 scores: bit c set where a[c] >= T
-__device__ __forceinline__ uint64_t screen_mask8(const int* a, int T) {
-  constexpr int C = 49;
-  unsigned lo = 0u, hi = 0u;
-  unsigned long long s[C];
-#pragma unroll
-  for (int k = 0; k < C + 2; k++) {
-    if (k < C) asm volatile("v_cmp_ge_i32_e64 %0, %1, %2" : "=s"(s[k]) : "v"(a[C - 1 - k]), "v"(T));
-    if (k >= 2) {
-      unsigned long long co;  // the carry-out (dead)
-      if (C - 1 - (k - 2) >= 32)
-        asm volatile("v_addc_co_u32_e64 %0, %1, %0, %0, %2" : "+v"(hi), "=s"(co) : "s"(s[k - 2]));
-      else
-        asm volatile("v_addc_co_u32_e64 %0, %1, %0, %0, %2" : "+v"(lo), "=s"(co) : "s"(s[k - 2]));
-    }
-  }
-  return ((uint64_t)hi << 32) | lo;
-}
-
-// The int8-screened level: fill by layout and screen, integer threshold, mask, exact chains of the survivors from
-// D11h (L2) as in screened_level, re-centre
-template <int D, bool PLANAR>
-__device__ __forceinline__ void screened_level8(const TileCtx& t, const LevelWin& w, const LaneGrid& g, const h2* q,
-                                                int& cu, int& cv, h1& max_score, uint4* lds, bool first) {
-  constexpr int G = 7;
-  const int wid = t.wid, H = t.H, W = t.W;
-  int a[G * G];  // written by plane A's screen
-  __syncthreads();  // the reduction scratch aliases the window: its readers are done
-  rt_prio_from<RT_PRIO_START, RT_PRIO_FILL, D>();
-  if (w.one8) {  // both planes in one fill: plane A's 30 x 56 x 16 B, plane B behind it
+// The int8 screen of one level, likewise (a[]: int32 scores): plane A (16 channels) seeds a[], plane B adds the rest
+template <int D>
+__device__ __forceinline__ void screen_window(const TileCtx& t, const LevelWin& w, const LaneGrid& g, const h2*,
+                                              uint4* lds, int* a) {
+  const int wid = t.wid;
+  const unsigned* q8 = t.i8.q;
+  if (w.layout == Layout::ONE8) {  // both planes in one fill: plane A's 30 x 56 x 16 B, plane B behind it
     uint4* ldsB = &lds[RT_8ROWS * RT_8COLS];
     // plane A's rows wid, wid + 4, ..; plane B's row pairs dealt from the wave that follows A's last row
-    fill_rows8<RT_8COLS>(t, w, lds, ldsB, wid, 2 * ((wid - w.nrows) & (RT_WAVES - 1)));
+    fill_rows<false>(t, w, int8_plane_a(t, w), lds, RT_8COLS, wid);
+    fill_pairs8<RT_8COLS>(t, w, ldsB, 2 * ((wid - w.nrows) & (RT_WAVES - 1)));
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     rt_prio_from<RT_PRIO_FILL, RT_PRIO_SCORE, D>();
     if (g.in) {
       const int b0 = g.by * RT_8COLS + g.bx;
-      screen8_chunk<D, RT_8COLS, 4>(&lds[b0], &t.q8[0], a);
-      screen8_chunk<D, RT_8COLS, 2>(reinterpret_cast<const uint2*>(ldsB) + b0, &t.q8[4], a);
+      screen_chunk<D, RT_8COLS>(&lds[b0], &q8[0], a, true);
+      screen_chunk<D, RT_8COLS>(reinterpret_cast<const uint2*>(ldsB) + b0, &q8[4], a, false);
     }
   } else {  // the general window, one plane at a time
     const int b0 = g.by * RT_COLS + g.bx;
-    fill_rows8<RT_COLS>(t, w, lds, nullptr, wid, 0);
+    fill_rows<false>(t, w, int8_plane_a(t, w), lds, RT_COLS, wid);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     rt_prio_from<RT_PRIO_FILL, RT_PRIO_SCORE, D>();
-    if (g.in) screen8_chunk<D, RT_COLS, 4>(&lds[b0], &t.q8[0], a);
+    if (g.in) screen_chunk<D>(&lds[b0], &q8[0], a, true);
     rt_prio_from<RT_PRIO_SCORE, RT_PRIO_FILL, D>();
     __syncthreads();  // plane A's readers are done
-    fill_rows8<RT_COLS>(t, w, nullptr, lds, 0, 2 * wid);
+    fill_pairs8<RT_COLS>(t, w, lds, 2 * wid);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     rt_prio_from<RT_PRIO_FILL, RT_PRIO_SCORE, D>();
-    if (g.in) screen8_chunk<D, RT_COLS, 2>(reinterpret_cast<const uint2*>(lds) + b0, &t.q8[4], a);
-  }
-  if (g.in) {
-    uint64_t vm = (1ull << (G * G)) - 1ull;  // in-image candidates
-    if (wave_leaves_image<D>(g, H, W)) {
-      vm = in_image_mask<D>(g.u_lo, g.v_lo, H, W);
-#pragma unroll
-      for (int c = 0; c < G * G; c++) a[c] = ((vm >> c) & 1ull) ? a[c] : INT_MIN;
-    }
-    // the level's best over the candidates that can win (screened_level: the centre cannot raise the threshold)
-    int lmax = a[0];
-#pragma unroll
-    for (int c = 1; c < G * G; c++)
-      if (c != G * G / 2) lmax = max(lmax, a[c]);
-    lmax = max(lmax, first ? a[G * G / 2] : INT_MIN);
-    // thresholds, rounded towards more survivors; the wave-uniform no-survivor skip as in screened_level (the second
-    // term never exceeds lmax)
-    const int tms = floor_i32(((float)max_score - t.b8) * RT_K8) - 1;
-    if (__builtin_amdgcn_readfirstlane((int)(__ballot(!t.sok8 || lmax >= tms) != 0ull)) == 0) return;
-    const int T = max(tms, floor_i32((float)lmax - 2.0f * t.b8 * RT_K8) - 1);
-    uint64_t m = screen_mask8(a, T);
-    if (!t.sok8) m = ~0ull;
-    m &= vm;
-    if (!first) m &= ~(1ull << (G * G / 2));
-    stats_survivors<D>(t.lane, m);
-    int bi = -1;
-    exact_survivors<D, PLANAR>(t.img, H, W, q, g.u_lo, g.v_lo, m, max_score, bi);
-    recentre<D>(g, bi, cu, cv);
+    if (g.in) screen_chunk<D>(reinterpret_cast<const uint2*>(lds) + b0, &q8[4], a, false);
   }
 }
+
+// The screened level: fill by layout and screen (screen_window of the kind's accumulator), then the tail
+template <int D, class K>
+__device__ __forceinline__ void screened_level(const TileCtx& t, const LevelWin& w, const LaneGrid& g, const h2* q,
+                                               int& cu, int& cv, h1& max_score, uint4* lds, bool first) {
+  typename K::acc_t a[49];  // written by the screen's first chunk or plane (seed): no zeroing
+  __syncthreads();  // the reduction scratch aliases the window: its readers are done
+  rt_prio_from<RT_PRIO_START, RT_PRIO_FILL, D>();
+  screen_window<D>(t, w, g, q, lds, a);
+  if (g.in) screened_tail<D, K>(t, w, g, q, a, cu, cv, max_score, lds, first);
+}
+
 
 // The exact scan's step over the 49 scores, in scan order (u outer, v inner), strict '>'. MASKED: only the candidates
 // of vm take part
@@ -875,17 +897,15 @@ __device__ __forceinline__ void refine_level(const TileCtx& t, bool active, cons
   g.by = g.v_lo - w.wy0;
   g.in = active && g.bx >= 0 && g.bx + 2 * RD < w.ncols && g.by >= 0 && g.by + 2 * RD < w.nrows;
   level_outliers<D, PLANAR>(t, active && !g.in, q, cu, cv, max_score);
-  if constexpr (SCREEN && PLANAR && D >= RT_S8_DMIN) {
-    if (t.s8)  // block-uniform
-      screened_level8<D, PLANAR>(t, w, g, q, cu, cv, max_score, lds, first);
-    else
-      screened_level<D, PLANAR>(t, w, g, q, cu, cv, max_score, lds, first);
-  } else if constexpr (SCREEN)
-    screened_level<D, PLANAR>(t, w, g, q, cu, cv, max_score, lds, first);
-  else
+  if constexpr (!SCREEN)
     exact_level<D, PLANAR>(t, w, g, q, cu, cv, max_score, lds);
+  else if constexpr (D < RT_S8_DMIN)
+    screened_level<D, ScreenF16>(t, w, g, q, cu, cv, max_score, lds, first);
+  else if (t.i8.on)  // block-uniform
+    screened_level<D, ScreenI8>(t, w, g, q, cu, cv, max_score, lds, first);
+  else
+    screened_level<D, ScreenF16>(t, w, g, q, cu, cv, max_score, lds, first);
 }
-
 
 template <bool P1_I64>
 __device__ __forceinline__ void load_p1(const void* p1v, size_t bn, int& cu, int& cv) {
@@ -940,10 +960,10 @@ __device__ __forceinline__ void proj_prologue(const TileCtx& t, const ProjArgs& 
     // reduce_cnorm's loads, in flight beside the pixel's own (4 KB from L2 at 512x512)
     // (with the int8 copy: the three runs norm, max component, max 1-norm)
     if (t.wid == 0) {
-      if (t.img8 != nullptr)
-        reduce_cnorm3_wave(pa.cnorm_part, pa.nparts, cmax_w);
+      if (t.i8.img != nullptr)
+        reduce_cnorm_wave<3>(pa.cnorm_part, pa.nparts, cmax_w);
       else
-        cmax_w[0] = reduce_cnorm_wave(pa.cnorm_part, pa.nparts);
+        reduce_cnorm_wave<1>(pa.cnorm_part, pa.nparts, cmax_w);
     }
   }
   const float nrm = fmaxf(norm3_ref(x, y, z), 1e-12f);  // F.normalize (matching.py:44)
@@ -1012,20 +1032,10 @@ __device__ __forceinline__ void tile_flow(TileCtx& t, bool active, int cu, int c
   t.tcv = ty * RT_TH + RT_TH / 2 + t.fv;
 }
 
-// SCREEN: the lane's bound B from its query's norm and the descriptor-norm bound cm (t.bq, t.sok; derivation in the
-// header comment of screen_chunk)
-__device__ __forceinline__ void screen_bound(TileCtx& t, const h2* q, float cm) {
-  float qq = 0.0f;
-#pragma unroll
-  for (int k = 0; k < 12; k++) qq = __builtin_amdgcn_fdot2(q[k], q[k], qq, false);
-  const float pq = sqrtf(qq) * cm * 1.001f;  // |q|_2 |c|_2 bound, rounded up
-  t.sok = pq <= 16384.0f;                         // false for NaN / inf
-  t.bq = t.sok ? 0.0125f * pq + 0x1p-18f : 0.0f;
-}
-
 // P1_I64: p1 given as (B,N,2) int64 (reference op) else int32 (fused); LIN_OUT: write idx = u + W v.
-// SCREEN: bound-screened scoring (cmaxp = the descriptor-norm bound written by prep / proj_occlusion).
 // LIN_OUT (fused path) reads the PLANAR D11h of prep_rays_kernel.
+// SCREEN (LIN_OUT instances only): bound-screened scoring (cmaxp = the descriptor-norm bound written by prep /
+// proj_occlusion).
 // FUSE_PROJ: the launch also runs the projection search (proj_occlusion_kernel's arithmetic in its order, from the
 // shared m3s_proj.hpp, so the centres and valid are bit-identical): each lane projects its own pixel, keeps the
 // centre in registers (no p1 traffic), writes valid and goes on into the levels; one wave per block reduces prep's
@@ -1039,6 +1049,7 @@ __global__ void __launch_bounds__(RT_THREADS, RT_MIN_BLOCKS)
                        const ProjArgs pa) {
   constexpr int F = 24;
   static_assert(!FUSE_PROJ || (D21_F32 && !P1_I64 && LIN_OUT), "the fused projection feeds the fused match path");
+  static_assert(!SCREEN || LIN_OUT, "the screens read the fused path's PLANAR D11h (and its int8 copy)");
   const unsigned long long stamp_top = bstamp_clock();
   __shared__ uint4 lds[RT_ROWS * RT_COLS];
   int(*s_red)[4] = reinterpret_cast<int(*)[4]>(&lds[0]);  // level-start reductions alias the window
@@ -1063,7 +1074,7 @@ __global__ void __launch_bounds__(RT_THREADS, RT_MIN_BLOCKS)
   const int N = H * W;
   const size_t bn = (size_t)b * N + (size_t)t.v_pix * W + t.u_pix;
   t.img = D11h + (size_t)b * N * F;
-  if constexpr (SCREEN && LIN_OUT) t.img8 = D8 != nullptr ? D8 + (size_t)b * N * F : nullptr;
+  if constexpr (SCREEN) t.i8.img = D8 != nullptr ? D8 + (size_t)b * N * F : nullptr;
   h2 q[F / 2];
   int cu = 0, cv = 0;
   float4 dv[F / 4];   // FUSE_PROJ: the raw D21 row, converted where it is first needed
@@ -1093,11 +1104,9 @@ __global__ void __launch_bounds__(RT_THREADS, RT_MIN_BLOCKS)
   }
   if constexpr (SCREEN) {
     screen_bound(t, q, FUSE_PROJ ? cmax_b[0] : cmaxp[0]);
-    if constexpr (LIN_OUT) {
-      // (cmaxp holds three floats when the copy is there)
-      if (t.img8 != nullptr && dilation_max >= RT_S8_DMIN)
-        screen_bound8(t, q, FUSE_PROJ ? cmax_b[1] : cmaxp[1], FUSE_PROJ ? cmax_b[2] : cmaxp[2]);
-    }
+    // (cmaxp holds three floats when the copy is there)
+    if (t.i8.img != nullptr && dilation_max >= RT_S8_DMIN)
+      screen_bound8(t, q, FUSE_PROJ ? cmax_b[1] : cmaxp[1], FUSE_PROJ ? cmax_b[2] : cmaxp[2]);
   }
   bstamp_levels_start(FUSE_PROJ, stamp_top);
   h1 max_score = (h1)0.0f;   // numeric_limits<c10::Half>::min() == +0, never reset between levels

@@ -5,7 +5,7 @@ levels d = dmax..1 run with the exact c10::Half chain deciding every level (the 
 centres follow the kernel's path), and per level both survivor rules are applied to the same candidates:
 
   f16   S = fp32 dot of the half operands (v_dot2c's value to ~1e-7), survivors S >= max(ms - B, lmax - 2 B)
-  int8  S8 = sum q8 c8 (exact), survivors S8 >= T8, the integer threshold of refine.hip screened_level8 from
+  int8  S8 = sum q8 c8 (exact), survivors S8 >= T8, the integer threshold of refine.hip ScreenI8 from
         B8 = B + E8 (tests/refine_screen8_cases.py has the restatement)
 
 with the centre dropped after the first level, as the kernel does. Every lane is counted (the kernel scores window

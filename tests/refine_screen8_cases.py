@@ -1,4 +1,4 @@
-"""Cases and the numpy restatement for the int8 pre-screen of the refine levels d >= 2 (refine.hip screened_level8).
+"""Cases and the numpy restatement for the int8 pre-screen of the refine levels d >= 2 (refine.hip ScreenI8).
 
 Restatement (exact, from the half-rounded values, as prep_rays_kernel and screen_bound8 compute them):
   quantise8(x_h)  = clamp(rint(127 x_h), -127, 127), rint = round-half-even; 127 x_h is exact in fp32

@@ -1,4 +1,4 @@
-"""GPU parity of the int8 pre-screen at the refine levels d >= 2 (refine.hip screened_level8).
+"""GPU parity of the int8 pre-screen at the refine levels d >= 2 (refine.hip ScreenI8).
 
 match()'s idx and valid must be bit-identical with the path on (default), with M3S_REFINE_SCREEN8=0 (the f16 screen at
 every level) and with M3S_REFINE_SCREEN=0 (the exact scan), and equal to the oracle. No tolerances. The cases

@@ -1,4 +1,4 @@
-"""Host checks of the int8 pre-screen's arithmetic (refine.hip screened_level8, matching.hip desc_planar), no GPU.
+"""Host checks of the int8 pre-screen's arithmetic (refine.hip ScreenI8, matching.hip desc_planar), no GPU.
 
 * the bound: |S_half_chain - S8 / 127^2| <= B8 = B + E8 over > 10^5 operand pairs (components at +-1, zeros, half
   subnormals, worst-case sign patterns), the half chain with the oracle's rounding;
